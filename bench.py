@@ -16,9 +16,15 @@ Other BASELINE configs (reported the same way, selected with --config):
      sums + cost/gCO2/SLO Pareto frontier exchanged with RCCL all-gather
   5  learned MLP policy 64->256->256->8, bf16 MFMA, 1e7 states per GPU
 
-Prints ONE JSON line (rank 0). Fields beyond the driver contract:
-  roofline      of the dominant kernel (HIP-event duration on the engine stream)
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps
+steps, writes --dump-outputs if asked and prints the line; its roofline block
+is arithmetic on the timed steps' own HIP-event durations. Everything that
+takes work of its own is behind --full:
   cpu_baseline  the CPU oracle (plain C, same semantics) on a bounded sample
+  parity        the GPU rollout against that oracle, field by field
+  totals        the device totals through the RCCL all-reduce
+  roofline      .copy_gbs (a measured 2 GiB device copy), .traffic and issue
+                (copied from the committed profiles)
 """
 import argparse
 import ctypes as C
@@ -51,8 +57,16 @@ def main():
                     help="config 5: 'policy' = the closed-loop policy rollout (MLP in the loop every step); "
                          "'grad' = the differentiable-control step: a stochastic closed-loop rollout plus the "
                          "score-function gradient of E[cost + w gCO2 + w SLO] (ccka_policy_grad)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU baseline duration")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the CPU baseline "
+                         "and the parity check against the CPU oracle (unless --no-cpu), the device totals through "
+                         "the RCCL all-reduce, the measured device copy ceiling and the figures copied from the "
+                         "committed profiles")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float64 / "
+                         "float32; a fixed seeded sample of the larger arrays, see dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: target CPU baseline duration")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline and the parity check")
     ap.add_argument("--drift", action="store_true",
                     help="configs 2-4 with Karpenter drift at the zone switch (SEMANTICS 3.G0; general kernel)")
     ap.add_argument("--replace", action="store_true",
@@ -90,6 +104,8 @@ def main():
     ap.add_argument("--spawn", action="store_true",
                     help="run the ranks as fresh child processes even at --gpus 1 (the launcher path)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.deployments > 1 and (args.config != 2 or args.keda):
         ap.error("--deployments applies to config 2 with HPA deployments only (not with --keda)")
 
@@ -104,10 +120,10 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
-    import torch
-
-    dist = None
+    # torch carries the cross-rank plumbing only: one rank runs on libccka alone
+    torch = dist = None
     if world > 1:
+        import torch
         import torch.distributed as dist
 
         torch.cuda.set_device(local)
@@ -136,7 +152,7 @@ def main():
     def barrier():
         if dist is not None:
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
         eng.sync()
 
     cfg = args.config
@@ -146,6 +162,7 @@ def main():
     spec = sc = None
     policy = cfg == 5 and args.mode in ("policy", "grad")
     grad = cfg == 5 and args.mode == "grad"
+    last = {}  # what the last step returned to its caller on the host (--dump-outputs)
     if policy:
         # closed loop: every step featurize -> MLP (bf16 MFMA) -> actions -> one rollout step
         N = args.n or (250_000 if grad else 1_000_000)
@@ -169,7 +186,8 @@ def main():
 
         def step_fn():
             if grad:  # one policy-gradient step's data: rollout + MLP backward over N x T rows
-                grad_obj.append(eng.policy_grad(seed=len(grad_obj) + 1, w_carbon=0.05, w_slo=0.01)[1])
+                last["grads"], last["objective"] = eng.policy_grad(seed=len(grad_obj) + 1, w_carbon=0.05, w_slo=0.01)
+                grad_obj.append(last["objective"])
             else:
                 eng.policy_rollout(trajectory=False)
     elif cfg == 5:
@@ -246,7 +264,8 @@ def main():
         def step_fn():
             eng.rollout_async(trajectory=traj)
             if cfg == 4:  # per-grid sums + Pareto frontier (RCCL all-gather at N > 1)
-                frontier.append(len(eng.pareto(configs.CONFIG4_TRACES)))
+                last["pareto"] = eng.pareto(configs.CONFIG4_TRACES)
+                frontier.append(len(last["pareto"]))
 
     for _ in range(args.warmup):
         step_fn()
@@ -281,6 +300,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     eng, N, traj, last, mlp_forward=cfg == 5 and not policy, grad=grad)
     K = args.steps
     avg_ms = sum(kms) / len(kms)
     engine_id, table_ms = eng.last_engine() if cfg != 5 or policy else (0, 0.0)
@@ -337,15 +359,17 @@ def main():
                          "kernel": "mlp16_kernel" if args.mlp_tile == 16 else "mlp_kernel", "kernel_ms_avg": avg_ms,
                          "flops_per_launch": flops},
         }
-        if rank == 0 and world == 1 and not args.no_cpu:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline_mlp(args.cpu_seconds)
     else:
-        local_totals = eng.totals()
-        totals = abi.Totals.from_buffer_copy(local_totals)
-        if cfg != 4:
-            comm_init()
-        # the cross-GPU exchange of the totals: RCCL all-reduce inside libccka
-        eng._chk(eng.lib.ccka_allreduce_totals(eng.ctx, C.byref(totals)), "ccka_allreduce_totals")
+        local_totals = totals = None
+        if args.full:
+            local_totals = eng.totals()
+            totals = abi.Totals.from_buffer_copy(local_totals)
+            if cfg != 4:
+                comm_init()
+            # the cross-GPU exchange of the totals: RCCL all-reduce inside libccka
+            eng._chk(eng.lib.ccka_allreduce_totals(eng.ctx, C.byref(totals)), "ccka_allreduce_totals")
         steps_total = (N * world if cfg != 3 else N * world) * T * K
         value = steps_total / elapsed
         # algorithmic bytes per launch: load [T][N] int32 read once (config 4:
@@ -355,8 +379,8 @@ def main():
         load_cols = (configs.CONFIG4_TRACES if cfg == 4 else N) * len(spec.deploys)
         bytes_launch = load_cols * T * 4 + (N * T * 16 if traj else 0) + N * 6 + N * 72
         achieved = bytes_launch / (avg_ms * 1e-3) / 1e9
-        traffic, traffic_src = (None, None) if (args.drift or args.replace or args.multi or args.keda or
-                                                args.deployments > 1 or
+        traffic, traffic_src = (None, None) if (not args.full or args.drift or args.replace or args.multi or
+                                                args.keda or args.deployments > 1 or
                                                 args.hpa_sync not in (0, 60) or args.budget is not None or
                                                 args.trace_flat) else measured_traffic(cfg, traj, N, T)
         workloads = {
@@ -406,23 +430,24 @@ def main():
             # the kernel is issue-bound, not HBM-bound: its measured issue-side
             # utilisation (profiled) and the measured copy ceiling
             # (profiled on the single-deployment kernel only)
-            "issue": profiled_issue(cfg) if engine_id == 2 and not (args.drift or args.replace or args.multi or
-                                                                   args.keda or args.hpa_sync not in (0, 60)) else None,
-            "totals": {"cost_usd": totals.cost_uphmin / 6e7, "energy_kwh": totals.energy_wmin / 6e4,
-                       "gco2_kg": totals.gco2 / 1e3, "slo_minutes": totals.slo_minutes,
-                       "launches": totals.launches, "deletions": totals.deletions},
+            "issue": profiled_issue(cfg) if args.full and engine_id == 2 and not (
+                args.drift or args.replace or args.multi or args.keda or args.hpa_sync not in (0, 60)) else None,
+            "totals": None if totals is None else {
+                "cost_usd": totals.cost_uphmin / 6e7, "energy_kwh": totals.energy_wmin / 6e4,
+                "gco2_kg": totals.gco2 / 1e3, "slo_minutes": totals.slo_minutes,
+                "launches": totals.launches, "deletions": totals.deletions},
         }
         if cfg == 4:
             out["pareto_frontier_grids"] = frontier[-1] if frontier else None
-        if rank == 0:
+        if args.full and rank == 0:
             cbw = copy_bandwidth(eng)
             out["roofline"]["copy_gbs"] = cbw
             out["roofline"]["copy_kernel"] = "copy16_kernel: 2 GiB dwordx4 nontemporal copy, one element per thread, median of 5 (tools/probe/copyprobe.hip)"
             out["roofline"]["frac_of_copy"] = achieved / cbw
-        if rank == 0 and world == 1 and not args.no_cpu:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu:
             out["cpu_baseline"], out["parity"], out["parity_detail"] = cpu_baseline(
                 eng, spec, sc, args.cpu_seconds, traj, local_totals)
-        elif world > 1 and not args.no_cpu:
+        elif args.full and world > 1 and not args.no_cpu:
             # every rank: an untimed prefix of its own shard against the oracle
             ok, det = rank_parity(eng, spec, sc, traj)
             flags = [None] * world
@@ -444,6 +469,61 @@ def general_dims(d, maxn):
     slots (kernel_dims in csrc/kparams.h)."""
     dmax = 1 if d == 1 else 2 if d <= 2 else 4 if d <= 4 else 8 if d <= 8 else 12 if d <= 12 else 16
     return dmax, 8 if maxn <= 8 and dmax <= 4 else 16
+
+
+DUMP_ROWS = 65536      # scenarios (states) sampled from per-scenario outputs
+DUMP_TRAJ_COLS = 256   # scenarios whose whole [T] trajectory is kept
+
+
+def dump_sample(n, k):
+    """Sorted indices of at most k of n items: all of them when n <= k, else a
+    fixed draw (seed 0), so two builds run with the same arguments keep the
+    same items."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+
+
+def dump_outputs(path, eng, n, traj, last, mlp_forward, grad):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, as float64 .npy files (float32 for the MLP's fp32 outputs), about
+    25 MB at most:
+      rollouts      results_<field>.npy of DUMP_ROWS sampled scenarios (their
+                    indices in results_index.npy); in trajectory mode
+                    trajectory_<field>.npy [T][DUMP_TRAJ_COLS] (scenario
+                    indices in trajectory_index.npy); config 4 also
+                    pareto_<field>.npy, the frontier the last step returned
+      MLP forward   actions.npy, DUMP_ROWS sampled rows (actions_index.npy)
+      --mode grad   grad_<w1..b3>.npy, the last step's gradient, and
+                    objective.npy
+    Every integer field is below 2^53, so the float64 copy is exact."""
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a, dt=np.float64):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=dt))
+
+    if mlp_forward:
+        rows = dump_sample(n, DUMP_ROWS)
+        save("actions_index", rows)
+        save("actions", eng.mlp_actions()[rows], np.float32)
+        return
+    if grad:
+        for k, g in last["grads"].items():
+            save("grad_" + k, g, np.float32)
+        save("objective", [last["objective"]])
+    rows = dump_sample(n, DUMP_ROWS)
+    save("results_index", rows)
+    for k, a in eng.results().items():
+        save("results_" + k, a[rows])
+    if traj:
+        cols = dump_sample(n, DUMP_TRAJ_COLS)
+        save("trajectory_index", cols)
+        tr = eng.trajectory()
+        for f in tr.dtype.names:
+            save("trajectory_" + f, tr[f][:, cols])
+    if "pareto" in last:
+        for f in last["pareto"].dtype.names:
+            save("pareto_" + f, last["pareto"][f])
 
 
 def measured_traffic(cfg, traj, n, T):

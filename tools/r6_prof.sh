@@ -8,5 +8,5 @@ tools/gpu_step.sh pgtest 300 python -u -m pytest tests/test_gpu_pg.py -x -q --ti
 tools/gpu_step.sh p_c2 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof/c2 -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu || exit $?
 tools/gpu_step.sh p_dep2 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof/dep2 -o run --output-format csv -- python3 bench.py --deployments 2 --steps 10 --warmup 2 --no-cpu || exit $?
 tools/gpu_step.sh p_grad 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof/grad -o run --output-format csv -- python3 bench.py --config 5 --mode grad --steps 5 --warmup 1 --no-cpu || exit $?
-tools/gpu_step.sh grad 300 python -u bench.py --config 5 --mode grad --steps 5 --warmup 1 --no-cpu || exit $?
+tools/gpu_step.sh grad 300 python -u bench.py --full --config 5 --mode grad --steps 5 --warmup 1 --no-cpu || exit $?
 echo all-done
