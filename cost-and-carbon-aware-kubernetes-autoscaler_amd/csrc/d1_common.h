@@ -1,7 +1,6 @@
-// d1_common.h — device helpers shared by the single-deployment engines:
-// rollout_d1.hip (one wave per scenario batch, event steps per wave) and
-// rollout_pool.hip (event steps pooled per workgroup). Internal linkage: each
-// translation unit gets its own copy.
+// d1_common.h — device helpers of the single-deployment engine, rollout_d1.hip
+// (one wave per scenario batch, event steps per wave). Internal linkage: a
+// translation unit that includes it gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -625,7 +625,9 @@ constexpr bool kGKS = false;
 #ifndef SK_OCC2  // skewed instantiations at two waves per SIMD (variant builds)
 #define SK_OCC2 0
 #endif
-template <int DMAX, int MAXN, int POL = 0, int SK = 0>
+// LF2: the skewed schedule's lane-local provisioning branch is compiled in (a
+// template parameter, so every instantiation's body is the same text in every unit)
+template <int DMAX, int MAXN, int POL = 0, int SK = 0, int LF2 = 0>
 __global__ void __launch_bounds__(256, ((POL == 0 && DMAX == 1 && MAXN <= 8) || (SK && SK_OCC2)) ? 2 : 1)
     rollout_kernel(KParams p) {
   static_assert(POL == 0 || (DMAX == 1 && MAXN <= 8), "fused closed loop: one deployment, <= 8 slots");
@@ -992,9 +994,6 @@ __global__ void __launch_bounds__(256, ((POL == 0 && DMAX == 1 && MAXN <= 8) || 
   constexpr int SKS = SK ? (SK_S_V) : 1;  // quiet steps per iteration and lane
   constexpr int SKD = SK ? DMAX : 1;
   constexpr int UQ = 0x7fffffff;  // "any usage" threshold
-#ifndef SK_LANE_F2  // lane-local provisioning on the skewed schedule (variant builds)
-#define SK_LANE_F2 0
-#endif
 #ifndef SK_K_V  // full-step cadence in passes (variant builds)
 #define SK_K_V 1
 #endif
@@ -1782,8 +1781,8 @@ __global__ void __launch_bounds__(256, ((POL == 0 && DMAX == 1 && MAXN <= 8) || 
           }
         }
       }
-    } else if (SK && SK_LANE_F2 && p.lds_lclaims >= 0) {
-      // lane-local F2 (variant builds, SK_LANE_F2; measured 1-4 % slower than the
+    } else if (SK && LF2 && p.lds_lclaims >= 0) {
+      // lane-local F2 (variant builds, CCKA_SK_LF2; measured 1-4 % slower than the
       // cooperative scans on 2 / 4 deployments x 8 / 16 slots): every
       // lane that needs NodeClaims builds and launches them itself, by the
       // cooperative path's rules in the same order (claims of this step in

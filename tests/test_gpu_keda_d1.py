@@ -11,7 +11,7 @@ import pytest
 
 import pyoracle as po
 from ccka import abi, configs
-from ccka.world import deployment, default_down
+from ccka.world import ScenarioSet, deployment, default_down
 from parity import compare, oracle, run_engine
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +55,19 @@ def test_keda_single_deployment_parity(engine, case):
     reps = tc["replicas"]
     if case in ("activation", "cool0_max", "long_windows"):
         assert (reps[1:] == 0).any() and (reps > 0).any()  # scaled to zero and back
+
+
+def test_keda_from_zero_plain_scenarios(engine):
+    """Scale from zero with an activation threshold below the per-replica
+    threshold and a short cooldown, on scenarios without overrides."""
+    spec = keda_world(T=720, keda_threshold=700, keda_activation=300, keda_cooldown=180, keda_max=40)
+    sc = ScenarioSet(2113, 5)
+    load = po.gen_load(configs.trace_gen(9), spec.n_steps, 1, sc.n, first_id=5)
+    rg, tg = run_engine(engine, spec, sc, load=load, traj=True)
+    assert engine.last_engine()[0] == 2
+    rc, tc = oracle(spec, sc, load, traj=True, threads=THREADS)
+    assert rc["launches"].sum() > 0
+    compare(rg, rc, tg, tc)
 
 
 @pytest.mark.parametrize("lpw", [1, 33, 64])

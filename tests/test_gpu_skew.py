@@ -154,7 +154,7 @@ def test_skewed_schedule_not_used_where_it_does_not_hold(engine):
 @pytest.mark.parametrize("name", ["d2_n8_overrides", "d2_n16_limits", "d4_n8_delay0"])
 def test_skewed_schedule_cooperative_provisioning(engine, name):
     """ccka_debug_engine(3) (the skewed schedule with the wave-cooperative scans
-    forced; builds with SK_LANE_F2 otherwise provision lane-locally for small
+    forced; builds with CCKA_SK_LF2 otherwise provision lane-locally for small
     catalogs) and the default give the oracle's launches, bit for bit."""
     spec, sc = world(name)
     load = po.gen_load(configs.trace_gen(37), spec.n_steps, len(spec.deploys), sc.n, first_id=sc.first_id)

@@ -1,5 +1,6 @@
 """A/B of the skewed schedule's provisioning paths (ccka_debug_engine 0: lane-local
-NodeClaims where they fit in LDS, 3: the wave-cooperative scans) and of the lockstep
+NodeClaims where they fit in LDS, in variant builds of rollout_sk.hip with s@-DCCKA_SK_LF2=1
+(tools/build_variants.py); 3: the wave-cooperative scans) and of the lockstep
 kernel (2) on bench.py's --deployments worlds (1e5 x 1440, trajectory mode).
 Results must be identical across modes. SK_AB_LIBS=main,NAME,...: the main build and
 variant builds (csrc/build/variants/NAME), mode 0 only, results compared with the main
