@@ -1,0 +1,166 @@
+// abi_debug.cpp — libccka.so's internal hooks (not part of include/ccka.h):
+// the switches tests, tools and bench.py use to force an engine, a layout or a
+// diagnostic, the copy-ceiling probe, the phase stamps and the device info.
+#include <algorithm>
+#include <cstdio>
+#include <vector>
+
+#include "ctx.h"
+
+using namespace ccka;
+
+// the 12 diagnostic phase stamps, allocated once and zeroed on the stream
+int stamps_buffer(ccka_ctx* c, unsigned long long** out) {
+  if (!c->d_stamps.reserve(12)) return fail(c, CCKA_ENOMEM, "stamps alloc");
+  HIPCHK(c, hipMemsetAsync(c->d_stamps, 0, 12 * sizeof(unsigned long long), c->stream));
+  *out = c->d_stamps;
+  return CCKA_OK;
+}
+
+extern "C" {
+
+// Internal: the device copy ceiling, GB/s of read + write of a `bytes`-byte
+// dwordx4 streaming copy (launch_copy16), the median of `reps` launches timed
+// with HIP events on the engine's stream after one warm-up launch.
+int ccka_debug_copy_gbs(ccka_ctx* c, int64_t bytes, int32_t reps, double* gbs) {
+  if (!c || !gbs || bytes < (1 << 20) || reps < 1 || reps > 64) return CCKA_EINVAL;
+  (void)hipSetDevice(c->device);
+  bytes &= ~(int64_t)4095;
+  DevBuf<char> a, b;
+  if (!a.resize(bytes) || !b.resize(bytes))
+    return fail(c, CCKA_ENOMEM, "copy probe alloc (2 x %lld bytes)", (long long)bytes);
+  int rc = CCKA_OK;
+  std::vector<float> ms((size_t)reps);
+  hipEvent_t e0 = nullptr, e1 = nullptr;  // own events: ccka_last_kernel_ms keeps the rollout's
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
+    rc = fail(c, CCKA_EHIP, "copy probe events");
+  if (rc == CCKA_OK && (hipMemsetAsync(a, 1, (size_t)bytes, c->stream) != hipSuccess ||
+      launch_copy16(a, b, bytes, c->cus, c->stream) != hipSuccess))
+    rc = fail(c, CCKA_EHIP, "copy probe warm-up");
+  for (int k = 0; k < reps && rc == CCKA_OK; ++k) {
+    if (hipEventRecord(e0, c->stream) != hipSuccess || launch_copy16(a, b, bytes, c->cus, c->stream) != hipSuccess ||
+        hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+        hipEventElapsedTime(&ms[(size_t)k], e0, e1) != hipSuccess)
+      rc = fail(c, CCKA_EHIP, "copy probe launch %d", k);
+  }
+  (void)hipStreamSynchronize(c->stream);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (rc != CCKA_OK) return rc;
+  std::sort(ms.begin(), ms.end());
+  *gbs = 2.0 * (double)bytes / ((double)ms[(size_t)reps / 2] * 1e-3) / 1e9;
+  return CCKA_OK;
+}
+
+// Internal profiling hook: phase-ablation mask for timing attribution only;
+// results of an ablated run are meaningless.
+int ccka_debug_ablate(ccka_ctx* c, int32_t mask) {
+  if (!c) return CCKA_EINVAL;
+  c->ablate = mask;
+  return CCKA_OK;
+}
+
+// Internal: 0 = choose the engine automatically, 1 = always the general kernel
+// (tests compare both engines), 2 = the general kernel in lockstep (no
+// lane-skewed schedule for several deployments), 3 = automatic with the skewed
+// schedule's provisioning on the wave-cooperative scans (A/B of the lane-local one).
+int ccka_debug_engine(ccka_ctx* c, int32_t mode) {
+  if (!c || mode < 0 || mode > 3) return CCKA_EINVAL;
+  c->sk_coop_f2 = mode == 3;
+  c->engine_mode = mode == 3 ? 0 : mode;
+  return CCKA_OK;
+}
+
+// Internal: which engine ran last (1 general, 2 single-deployment, 3 the
+// launched closed loop, 4 the fused closed loop, 5 the general kernel on the
+// lane-skewed schedule) and the duration of its argmin-table kernel.
+int ccka_debug_last_engine(ccka_ctx* c, int32_t* engine, double* table_ms) {
+  if (!c) return CCKA_EINVAL;
+  if (engine) *engine = c->last_engine;
+  if (table_ms) *table_ms = c->last_table_ms;
+  return CCKA_OK;
+}
+
+// Internal: rows per policy-gradient backward chunk (multiple of 32; 0 = the
+// default 2^23), to exercise the chunked sum at test sizes.
+int ccka_debug_pg_chunk(ccka_ctx* c, int64_t rows) {
+  if (!c || rows < 0 || rows % 32) return CCKA_EINVAL;
+  c->pg_chunk = rows;
+  return CCKA_OK;
+}
+
+// Internal: 0 = the fused loop scans the catalog for its launches (A/B of the
+// argmin tables; same results).
+int ccka_debug_policy_table(ccka_ctx* c, int32_t on) {
+  if (!c) return CCKA_EINVAL;
+  c->pol_table_off = on == 0;
+  return CCKA_OK;
+}
+
+// Internal: 0 = the launched closed loop even where the fused one applies.
+int ccka_debug_policy_fused(ccka_ctx* c, int32_t on) {
+  if (!c) return CCKA_EINVAL;
+  c->pol_fused_off = on == 0;
+  return CCKA_OK;
+}
+
+// Internal: 0 = enqueue the closed loop's launches directly instead of
+// replaying its captured hipGraph (1, the default).
+int ccka_debug_policy_graph(ccka_ctx* c, int32_t on) {
+  if (!c) return CCKA_EINVAL;
+  c->pol_graph_off = on == 0;
+  return CCKA_OK;
+}
+
+// Internal: scenarios per wave of the single-deployment kernel (1..64; 0 = automatic).
+int ccka_debug_lpw(ccka_ctx* c, int32_t lpw) {
+  if (!c || lpw < 0 || lpw > 64) return CCKA_EINVAL;
+  c->lpw = lpw;
+  return CCKA_OK;
+}
+
+// Internal: 1 = the single-deployment kernel reads the [T][N] trace instead of
+// its wave-tiled copy (layout A/B; results are the same).
+int ccka_debug_trace_flat(ccka_ctx* c, int32_t on) {
+  if (!c) return CCKA_EINVAL;
+  c->trace_flat = on != 0;
+  return CCKA_OK;
+}
+
+// Internal: occupancy target of the single-deployment kernel (2, 3; 0 = automatic).
+int ccka_debug_occ(ccka_ctx* c, int32_t occ) {
+  if (!c || occ < 0 || occ > 3 || occ == 1) return CCKA_EINVAL;
+  c->occ = occ;
+  return CCKA_OK;
+}
+
+// Internal: the standalone forward's MFMA tile (16: mlp16_kernel, 32: mlp_kernel).
+int ccka_debug_mlp_tile(ccka_ctx* c, int32_t tile) {
+  if (!c || (tile != 16 && tile != 32)) return CCKA_EINVAL;
+  c->mlp_tile = tile;
+  return CCKA_OK;
+}
+
+// Internal: diagnostic phase stamps of the MLP kernel (read with ccka_debug_stamps).
+int ccka_debug_mlp_stamps(ccka_ctx* c, int32_t enable) {
+  if (!c) return CCKA_EINVAL;
+  c->mlp_stamps = enable != 0;
+  return CCKA_OK;
+}
+
+// Internal: per-phase cycle totals of the last stamped run (ablate bit 16, or
+// ccka_debug_mlp_stamps), 12 words.
+int ccka_debug_stamps(ccka_ctx* c, unsigned long long* out8) {
+  if (!c || !out8 || !c->d_stamps) return CCKA_EINVAL;
+  HIPCHK(c, hipMemcpy(out8, c->d_stamps, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return CCKA_OK;
+}
+
+int ccka_device_info(ccka_ctx* c, char* name, int32_t name_len, int32_t* cu_count) {
+  if (!c) return CCKA_EINVAL;
+  if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", c->name);
+  if (cu_count) *cu_count = c->cus;
+  return CCKA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,184 @@
+// devbuf_test.cpp — DevBuf (devbuf.h) over a malloc-backed allocator that counts
+// its calls and can be told to fail the next k of them. Host only, built with
+// AddressSanitizer + UndefinedBehaviorSanitizer by `make devbuf-test`
+// (tests/test_devbuf.py): a leak, a double free or a use after free aborts it.
+#define CCKA_DEVBUF_NO_HIP
+#include "devbuf.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <type_traits>
+#include <utility>
+
+struct CountingAlloc {
+  static inline long allocs = 0, frees = 0, calls = 0, fail_next = 0;
+  static void* alloc(size_t bytes) {
+    ++calls;
+    if (fail_next > 0) {
+      --fail_next;
+      return nullptr;
+    }
+    ++allocs;
+    return std::malloc(bytes);
+  }
+  static void free(void* p) {
+    ++frees;
+    std::free(p);
+  }
+};
+using A = CountingAlloc;
+template <class T>
+using Buf = ccka::DevBuf<T, CountingAlloc>;
+
+static_assert(!std::is_copy_constructible<Buf<int>>::value, "DevBuf must not be copyable");
+static_assert(!std::is_copy_assignable<Buf<int>>::value, "DevBuf must not be copyable");
+static_assert(std::is_nothrow_move_constructible<Buf<int>>::value, "DevBuf moves");
+static_assert(std::is_nothrow_move_assignable<Buf<int>>::value, "DevBuf moves");
+
+#define CHECK(x)                                                   \
+  do {                                                             \
+    if (!(x)) {                                                    \
+      std::fprintf(stderr, "%s:%d: CHECK(%s)\n", __FILE__, __LINE__, #x); \
+      std::exit(1);                                                \
+    }                                                              \
+  } while (0)
+
+template <class T>
+static bool empty(const Buf<T>& b) { return b.get() == nullptr && b.count() == 0; }
+
+static void test_reserve() {
+  Buf<int32_t> b;
+  CHECK(empty(b));
+  CHECK(b.reserve(0) && empty(b) && A::calls == 0);  // n == 0: empty, success, no allocation
+  CHECK(b.reserve(100) && b.get() && b.count() == 100);
+  int32_t* p = b.get();
+  for (int i = 0; i < 100; ++i) p[i] = i;  // the whole extent is ours (ASan checks)
+  CHECK(b.reserve(100) && b.get() == p && b.count() == 100);  // equal: kept
+  CHECK(b.reserve(7) && b.get() == p && b.count() == 100);    // smaller: kept
+  CHECK(b.reserve(0) && b.get() == p && b.count() == 100);
+  const long a0 = A::allocs, f0 = A::frees;
+  CHECK(b.reserve(101) && b.count() == 101);  // larger: a new allocation, the old one freed
+  CHECK(A::allocs == a0 + 1 && A::frees == f0 + 1);
+  b.get()[100] = 1;
+  int32_t* q = b;  // implicit conversion
+  CHECK(q == b.get());
+}
+
+static void test_resize() {
+  Buf<double> b;
+  CHECK(b.resize(0) && empty(b));
+  CHECK(b.resize(64) && b.count() == 64);
+  double* p = b.get();
+  const long a0 = A::allocs, f0 = A::frees;
+  CHECK(b.resize(64) && b.get() == p && A::allocs == a0);  // equal: kept
+  CHECK(b.resize(63) && b.count() == 63 && A::allocs == a0 + 1 && A::frees == f0 + 1);  // smaller: reallocated
+  b.get()[62] = 1.0;
+  CHECK(b.resize(65) && b.count() == 65 && A::allocs == a0 + 2 && A::frees == f0 + 2);  // larger: reallocated
+  b.get()[64] = 1.0;
+  CHECK(b.resize(0) && empty(b) && A::frees == f0 + 3);  // n == 0: empty, success
+}
+
+static void test_overflow() {
+  struct Wide { char c[4096]; };
+  Buf<Wide> b;
+  CHECK(b.reserve(4));
+  const long c0 = A::calls;
+  const int64_t big = INT64_MAX / 2;  // x 4096 bytes wraps size_t
+  CHECK(!b.reserve(big) && empty(b) && A::calls == c0);
+  CHECK(b.resize(4));
+  CHECK(!b.resize(big) && empty(b) && A::calls == c0 + 1);
+  CHECK(!b.resize(-1) && empty(b) && !b.reserve(-1) && A::calls == c0 + 1);
+  Buf<char> bytes;  // one byte per element: no count overflows, the allocator decides
+  A::fail_next = 1;
+  CHECK(!bytes.reserve(INT64_MAX) && empty(bytes) && A::calls == c0 + 2);
+}
+
+static void test_failure_and_recovery() {
+  Buf<int64_t> b;
+  CHECK(b.reserve(10));
+  A::fail_next = 1;
+  CHECK(!b.reserve(20) && empty(b));  // the old allocation is gone too, never a stale count
+  CHECK(b.reserve(5) && b.count() == 5);  // the next call recovers
+  b.get()[4] = 1;
+  A::fail_next = 1;
+  CHECK(!b.resize(6) && empty(b));
+  CHECK(b.resize(6) && b.count() == 6);
+  b.get()[5] = 1;
+  CHECK(A::fail_next == 0);
+}
+
+// buffers that are sized together, as the context's groups are
+struct Group {
+  Buf<int32_t> a;
+  Buf<double> b;
+  Buf<char> c;
+  bool reserve(int64_t n) { return ccka::all_or_none(a.reserve(n) && b.reserve(2 * n) && c.reserve(n), a, b, c); }
+};
+
+static void test_group() {
+  Group g;
+  CHECK(g.reserve(8) && g.a.count() == 8 && g.b.count() == 16 && g.c.count() == 8);
+  for (int second_fails = 0; second_fails < 2; ++second_fails) {
+    // the first member grows, a later one fails: every member is empty afterwards
+    A::fail_next = 0;
+    CHECK(g.reserve(8));
+    const long c0 = A::calls;
+    if (second_fails) {
+      CHECK(g.a.reserve(100));  // already large enough: the group call allocates b first
+      A::fail_next = 1;
+      CHECK(!g.reserve(100));
+      CHECK(A::calls == c0 + 2);
+    } else {
+      A::fail_next = 1;
+      CHECK(!g.reserve(100));
+      CHECK(A::calls == c0 + 1);  // && stops at the first failure
+    }
+    CHECK(empty(g.a) && empty(g.b) && empty(g.c));
+  }
+  CHECK(g.reserve(3) && g.a.count() == 3 && g.b.count() == 6 && g.c.count() == 3);  // and recovers
+}
+
+static void test_release() {
+  Buf<int> b;
+  b.release();  // empty: harmless
+  CHECK(b.reserve(3));
+  const long f0 = A::frees;
+  b.release();
+  CHECK(empty(b) && A::frees == f0 + 1);
+  b.release();  // twice: harmless
+  CHECK(empty(b) && A::frees == f0 + 1);
+}
+
+static void test_move() {
+  Buf<int> a;
+  CHECK(a.reserve(4));
+  int* pa = a.get();
+  const long f0 = A::frees;
+  Buf<int> b(std::move(a));  // construction: ownership moves, nothing freed
+  CHECK(empty(a) && b.get() == pa && b.count() == 4 && A::frees == f0);
+  Buf<int> c;
+  CHECK(c.reserve(9));
+  c = std::move(b);  // assignment: the overwritten target is freed
+  CHECK(empty(b) && c.get() == pa && c.count() == 4 && A::frees == f0 + 1);
+  Buf<int>& self = c;
+  c = std::move(self);  // self-assignment keeps the buffer
+  CHECK(c.get() == pa && c.count() == 4 && A::frees == f0 + 1);
+  c.get()[3] = 1;
+  Buf<int> d;
+  d = std::move(a);  // moving an empty buffer
+  CHECK(empty(d) && empty(a));
+}
+
+int main() {
+  test_reserve();
+  test_resize();
+  test_overflow();
+  test_failure_and_recovery();
+  test_group();
+  test_release();
+  test_move();
+  // every buffer above has left its scope: nothing outstanding
+  CHECK(A::allocs > 0 && A::allocs == A::frees);
+  std::printf("devbuf ok: %ld allocations, %ld frees\n", A::allocs, A::frees);
+  return 0;
+}

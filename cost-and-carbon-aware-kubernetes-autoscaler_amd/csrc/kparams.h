@@ -1,4 +1,4 @@
-// kparams.h — kernel argument blocks shared by rollout.hip and ccka_abi.cpp.
+// kparams.h — kernel argument blocks shared by the kernel units and the C ABI (abi_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -167,8 +167,8 @@ hipError_t launch_trace_nt(const int32_t* in, int32_t* out, int64_t NL, int64_t 
 
 // ---------------------------------------------------------------------------
 // Single-deployment HPA engine (rollout_d1.hip): every BASELINE config 2-4
-// workload. The host digests the world into this block (ccka_abi.cpp,
-// d1_eligible / d1_prepare); the Karpenter launch choice comes from the
+// workload. The host digests the world into this block (abi_ctx.cpp,
+// d1_check_world / d1_prepare); the Karpenter launch choice comes from the
 // per-rollout argmin tables built by launch_table.
 // ---------------------------------------------------------------------------
 constexpr int D1_MAX_ZI = 8;   // distinct NodePool zone masks

@@ -9,8 +9,8 @@
 // (column on the lane, rows in registers): registers 8s..8s+7, converted to
 // bf16, are k-step s of the next product with the permuted k order
 // k = 16s + 8(j>>2) + 4h + (j&3) (j = element, h = lane half). The host lays
-// the weight fragments out in exactly that order (ccka_abi.cpp,
-// mlp_fragments), so no activation ever moves between lanes or through LDS.
+// the weight fragments out in exactly that order (abi_mlp.cpp,
+// ccka_mlp_set_weights), so no activation ever moves between lanes or through LDS.
 //
 // Residency and schedule (one persistent 4-wave workgroup per CU, one wave
 // per SIMD): W1 fragments (32 KiB) in each wave's accumulation registers, W2

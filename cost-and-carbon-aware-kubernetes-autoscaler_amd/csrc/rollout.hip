@@ -618,7 +618,7 @@ constexpr bool kGKS = false;
 // every other step stalls the lane, and the wave runs the full step for all
 // its stalled lanes together (the single-deployment kernel's event batching,
 // rollout_d1.hip, for D <= 4 deployments). Host-checked preconditions
-// (sk_eligible in ccka_abi.cpp): HPA / static deployments, one decision per
+// (sk_eligible in abi_rollout.cpp): HPA / static deployments, one decision per
 // step over the register rings, every hour's price tiles in LDS, no detail,
 // drift, replacement or multi-node consolidation, the whole horizon in one
 // launch. Trajectory records scenario-major [N][T].
@@ -3375,7 +3375,7 @@ __global__ void totals_final(TotParams q, int nparts) {
 }
 
 // ---------------------------------------------------------------------------
-// launchers (called from ccka_abi.cpp)
+// launchers (called from the abi_*.cpp units)
 // ---------------------------------------------------------------------------
 hipError_t launch_gen_load(const GenParams& g, hipStream_t s) {
   dim3 grid((unsigned)((g.n + 255) / 256), (unsigned)g.D);

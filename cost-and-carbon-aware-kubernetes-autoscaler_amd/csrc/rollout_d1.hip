@@ -2052,7 +2052,7 @@ hipError_t launch_traj_transpose(const ccka_traj_rec* in, ccka_traj_rec* out, in
 // [T][N] load trace -> wave-tiled [wave][T][lpw] (the single-deployment
 // kernels' read layout: a wave's rows contiguous, every row lpw wide, the last
 // wave's padded: one row stride for all), once per trace / lanes-per-wave
-// change (ccka_abi.cpp d1_trace_tile); reads coalesced, writes in runs of lpw ints.
+// change (abi_rollout.cpp d1_trace_tile); reads coalesced, writes in runs of lpw ints.
 __global__ void __launch_bounds__(256) trace_tile_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out,
                                                          int64_t N, int64_t T, int64_t lpw) {
   const int64_t total = N * T, stride = (int64_t)gridDim.x * blockDim.x;

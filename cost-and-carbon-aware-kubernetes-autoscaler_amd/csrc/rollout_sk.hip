@@ -3,7 +3,7 @@
 // static deployments run their quiet steps per lane and their full steps in
 // per-wave batches of stalled lanes (the single-deployment kernel's event
 // batching, rollout_d1.hip, for several deployments). sk_eligible
-// (ccka_abi.cpp) checks the preconditions.
+// (abi_rollout.cpp) checks the preconditions.
 #define CCKA_ROLLOUT_PART 1
 #include "rollout.hip"
 

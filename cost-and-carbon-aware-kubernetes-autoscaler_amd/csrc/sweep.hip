@@ -2,7 +2,7 @@
 // load traces. Per-grid sums of the rollout results (fixed-order, so
 // deterministic) and the cost / gCO2 / SLO-minutes Pareto frontier
 // (local non-dominated candidates, exchanged with an RCCL
-// all-gather in ccka_abi.cpp, then the same filter on every rank).
+// all-gather in abi_sweep.cpp, then the same filter on every rank).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -6,7 +6,7 @@ linked with the main build's other objects. Profiling aid only.
 NAME=r@other.hip replaces rollout.hip (the general kernel) instead, NAME=p@other.hip pg.hip, NAME=m@other.hip
 mlp.hip (NAME=m@mlp.hip:-DX builds mlp.hip itself with extra flags), NAME=s@-DX rollout_sk.hip (the general
 kernel's lane-skewed schedule; -DCCKA_SK_ONE instantiates <2, 8> only, -DCCKA_SK_LF2=1 instantiates its kernels
-with the lane-local provisioning branch, which the main build's ccka_abi.o then switches on). Set VARIANTS_NO_MAKE=1 to link
+with the lane-local provisioning branch, which the main build's abi_rollout.o then switches on). Set VARIANTS_NO_MAKE=1 to link
 against the objects already built.
 usage: python tools/build_variants.py name=-DD1_S_V=3 [name2="-DA -DB" ...]"""
 import os
@@ -42,7 +42,8 @@ for name, out, obj, p in procs:
     assert p.wait() == 0, name
     others = [os.path.join(CSRC, "build", f) for f in ("rollout.o", "rollout_multi.o", "rollout_pol.o", "rollout_sk.o",
                                                        "rollout_sk416.o", "rollout_d1.o", "sweep.o", "mlp.o", "pg.o",
-                                                       "ccka_abi.o") if f != os.path.basename(obj)]
+                                                       "abi_ctx.o", "abi_rollout.o", "abi_policy.o", "abi_sweep.o",
+                                                       "abi_mlp.o", "abi_debug.o") if f != os.path.basename(obj)]
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o",
                     os.path.join(out, "libccka.so"), obj, *others, "-L/opt/rocm/lib", "-lrccl",
                     "-Wl,-rpath,/opt/rocm/lib"], check=True)
