@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 STEP_SECONDS = 60
 MAX_TYPES = 1024
 MAX_ZONES = 4
@@ -141,6 +141,28 @@ class GridStats(C.Structure):
                 ("slo_minutes", C.c_int64), ("gco2", C.c_double), ("energy_wmin", C.c_double)]
 
 
+STAT_SUM, STAT_QUANTILE, STAT_TAIL = 0, 1, 2
+STAT_KINDS = {"sum": STAT_SUM, "quantile": STAT_QUANTILE, "tail": STAT_TAIL}
+STAT_OBJECTIVES = ("cost", "slo", "gco2", "energy")  # the order of ccka_sweep_stat's arrays
+
+
+class SweepStat(C.Structure):
+    """ccka_sweep_stat: one statistic per sweep objective (docs/SEMANTICS.md 6)."""
+    _fields_ = [("kind", C.c_int32 * 4), ("q_ppm", C.c_int32 * 4)]
+
+
+def sweep_stat(cost=("sum",), slo=("sum",), gco2=("sum",), energy=("sum",)) -> SweepStat:
+    """SweepStat from one (kind[, q_ppm]) per objective: kind "sum", "quantile"
+    or "tail" (or a STAT_* value), q_ppm the quantile in parts per million,
+    e.g. sweep_stat(slo=("quantile", 950000)) for mean cost / gCO2, p95 SLO minutes."""
+    st = SweepStat()
+    for j, spec in enumerate((cost, slo, gco2, energy)):
+        spec = (spec,) if isinstance(spec, (str, int)) else tuple(spec)
+        st.kind[j] = STAT_KINDS[spec[0]] if isinstance(spec[0], str) else int(spec[0])
+        st.q_ppm[j] = int(spec[1]) if len(spec) > 1 else 0
+    return st
+
+
 class Detail(C.Structure):
     """ccka_detail: per-pool / base-group / per-deployment breakdown (ccka_set_detail)."""
     _fields_ = [("pool_cost_uphmin", C.c_int64 * MAX_POOLS), ("pool_energy_nwmin", C.c_int64 * MAX_POOLS),
@@ -176,7 +198,7 @@ class TraceGen(C.Structure):
 
 
 STRUCT_ORDER = [ItType, Pool, Deployment, World, Scenarios, Results, TrajRec, Totals, TraceGen,
-                GridStats, Detail]
+                GridStats, Detail, SweepStat]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ENGINE_LIB = os.path.join(os.path.dirname(PKG_DIR), "csrc", "build", "libccka.so")
@@ -246,6 +268,10 @@ def load_engine(path: str | None = None):
         "ccka_totals_pack": (C.c_int, [C.POINTER(Totals), C.c_int32, C.POINTER(C.c_int64), C.c_int32]),
         "ccka_totals_finish": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(Totals)]),
         "ccka_device_info": (C.c_int, [vp, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+        "ccka_sweep_rank": (C.c_int64, [C.c_int64, C.c_int32]),
+        "ccka_get_grid_stat": (C.c_int, [vp, C.c_int64, C.POINTER(SweepStat), C.POINTER(GridStats), C.c_int64]),
+        "ccka_pareto_frontier_stat": (C.c_int, [vp, C.c_int64, C.POINTER(SweepStat), C.POINTER(GridStats),
+                                                C.c_int32, C.POINTER(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -266,6 +292,7 @@ EXPORTED = [
     "ccka_mlp_forward_async", "ccka_mlp_get_actions", "ccka_set_detail", "ccka_get_detail",
     "ccka_policy_rollout", "ccka_get_policy_actions", "ccka_trajectory_layout", "ccka_get_trajectory_native",
     "ccka_policy_grad", "ccka_get_policy_samples", "ccka_mlp_backward", "ccka_totals_pack", "ccka_totals_finish",
+    "ccka_sweep_rank", "ccka_get_grid_stat", "ccka_pareto_frontier_stat",
 ]
 TOTALS_INT64, TOTALS_BLOCK = 10, 11  # CCKA_TOTALS_INT64, CCKA_TOTALS_BLOCK
 EOVERFLOW = -8

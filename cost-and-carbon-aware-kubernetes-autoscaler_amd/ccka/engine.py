@@ -193,13 +193,43 @@ class Engine:
                   "ccka_get_grid_stats")
         return _grid_array(a, ng)
 
-    def pareto(self, grid_size: int, capacity: int | None = None) -> np.ndarray:
+    def grid_stat(self, grid_size: int, stat: abi.SweepStat) -> np.ndarray:
+        """Per-grid rows with a chosen statistic per objective (abi.sweep_stat):
+        a sum, a quantile or a tail sum in each objective's field."""
+        ng = self.n // grid_size
+        a = (abi.GridStats * ng)()
+        self._chk(self.lib.ccka_get_grid_stat(self.ctx, C.c_int64(grid_size), C.byref(stat), a, C.c_int64(ng)),
+                  "ccka_get_grid_stat")
+        return _grid_array(a, ng)
+
+    def pareto(self, grid_size: int, capacity: int | None = None, stat: abi.SweepStat | None = None) -> np.ndarray:
+        """The cost / gCO2 / SLO frontier of the grids' sums, or with `stat` of
+        their chosen statistics (ccka_pareto_frontier_stat)."""
         cap = capacity if capacity is not None else max(1, self.n // grid_size) * 8
         a = (abi.GridStats * cap)()
         n = C.c_int32()
-        self._chk(self.lib.ccka_pareto_frontier(self.ctx, C.c_int64(grid_size), a, cap, C.byref(n)),
-                  "ccka_pareto_frontier")
+        if stat is None:
+            self._chk(self.lib.ccka_pareto_frontier(self.ctx, C.c_int64(grid_size), a, cap, C.byref(n)),
+                      "ccka_pareto_frontier")
+        else:
+            self._chk(self.lib.ccka_pareto_frontier_stat(self.ctx, C.c_int64(grid_size), C.byref(stat), a, cap,
+                                                         C.byref(n)), "ccka_pareto_frontier_stat")
         return _grid_array(a, n.value)
+
+    def debug_grid_stat(self, cost, slo, gco2, energy, grid_size: int, stat: abi.SweepStat) -> np.ndarray:
+        """Internal: grid_stat's kernel path on given result columns (int64,
+        int32, float64, float64; whole grids of grid_size, grid ids from 0)."""
+        cols = [np.ascontiguousarray(a, dt) for a, dt in
+                ((cost, np.int64), (slo, np.int32), (gco2, np.float64), (energy, np.float64))]
+        n = len(cols[0])
+        assert all(a.shape == (n,) for a in cols)
+        ng = n // max(1, grid_size)
+        out = (abi.GridStats * max(1, ng))()
+        fn = self.lib.ccka_debug_grid_stat
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.POINTER(abi.SweepStat), C.c_void_p]
+        self._chk(fn(self.ctx, *[a.ctypes.data for a in cols], n, grid_size, C.byref(stat), out),
+                  "ccka_debug_grid_stat")
+        return _grid_array(out, ng)
 
     # ---- multi-GPU (RCCL over xGMI) ----
     def comm_init(self, uid: bytes | None = None, nranks: int = 1, rank: int = 0):

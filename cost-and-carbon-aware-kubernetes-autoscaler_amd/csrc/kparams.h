@@ -309,6 +309,16 @@ struct GridSrc {
   int64_t grid_size, first_grid, n_grids;
 };
 hipError_t launch_grid_stats(const GridSrc& g, ccka_grid_stats* out, hipStream_t s);
+// order statistics per grid (SEMANTICS 6), objectives in ccka_sweep_stat's
+// order: rank[j] = the nearest rank k of objective j (1 .. grid_size)
+struct GridSel {
+  GridSrc g;
+  int64_t rank[4];
+  int32_t kind[4];  // CCKA_STAT_*
+};
+// overwrites the QUANTILE / TAIL objectives' fields of out[0..n_grids); the
+// rest of each row (launch_grid_stats wrote it) stays
+hipError_t launch_grid_select(const GridSel& q, ccka_grid_stats* out, hipStream_t s);
 // streaming 16-byte-per-lane device copy (the measured copy ceiling of bench.py)
 hipError_t launch_copy16(const void* in, void* out, int64_t bytes, int cus, hipStream_t s);
 // non-dominated entries of in[0..n) (n may be device-resident: *n_dev if n < 0),

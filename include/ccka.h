@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CCKA_ABI_VERSION 5
+#define CCKA_ABI_VERSION 6
 
 #define CCKA_STEP_SECONDS 60
 #define CCKA_MAX_TYPES 1024
@@ -308,6 +308,21 @@ typedef struct ccka_grid_stats {
   double energy_wmin;
 } ccka_grid_stats;
 
+/* Per-grid statistic of one objective of a policy sweep (docs/SEMANTICS.md
+ * §6). With the grid's n values sorted ascending, x(1) <= ... <= x(n), and the
+ * nearest rank k = max(1, ceil(q_ppm * n / 1e6)) (integers only: ccka_sweep_rank):
+ * SUM the sum ccka_get_grid_stats returns, QUANTILE x(k) (always an element of
+ * the input), TAIL x(k) + ... + x(n) (n - k + 1 terms; dividing by that count
+ * gives the expected shortfall). */
+enum { CCKA_STAT_SUM = 0, CCKA_STAT_QUANTILE = 1, CCKA_STAT_TAIL = 2 };
+/* One statistic per objective, in the order cost_uphmin, slo_minutes, gco2,
+ * energy_wmin. q_ppm: the quantile in parts per million, 0 (the minimum) ..
+ * 1000000 (the maximum); ignored for SUM. 32 bytes. */
+typedef struct ccka_sweep_stat {
+  int32_t kind[4];
+  int32_t q_ppm[4];
+} ccka_sweep_stat;
+
 /* Synthetic load-trace generator (docs/SEMANTICS.md §4). */
 typedef struct ccka_trace_gen {
   uint64_t seed;
@@ -325,7 +340,7 @@ typedef struct ccka_ctx ccka_ctx;
 int32_t ccka_abi_version(void);
 /* sizes of the ABI structs, for binding self-checks: fills out[0..n) in the
  * order itype, pool, deployment, world, scenarios, results, traj_rec, totals,
- * trace_gen, grid_stats, detail; returns the count written. */
+ * trace_gen, grid_stats, detail, sweep_stat; returns the count written. */
 int32_t ccka_struct_sizes(int64_t* out, int32_t n);
 int ccka_open(ccka_ctx** out, int device_ordinal);
 void ccka_close(ccka_ctx* ctx);
@@ -397,6 +412,23 @@ int ccka_get_grid_stats(ccka_ctx* ctx, int64_t grid_size, ccka_grid_stats* out, 
  * capacity). Every rank must hold the same number of grids. */
 int ccka_pareto_frontier(ccka_ctx* ctx, int64_t grid_size, ccka_grid_stats* out, int32_t capacity,
                          int32_t* n_out);
+/* The nearest rank k = max(1, ceil(q_ppm * n / 1e6)) of ccka_sweep_stat, in
+ * integers (no context needed); -1 for n < 1 or q_ppm outside [0, 1000000]. */
+int64_t ccka_sweep_rank(int64_t n, int32_t q_ppm);
+/* ccka_get_grid_stats with a chosen statistic per objective: out[g] holds grid,
+ * scenarios, and in each objective's field its statistic over the grid (SUM
+ * fields are the sums of ccka_get_grid_stats bit for bit; QUANTILE and TAIL
+ * come from an exact selection on the device, no sort, deterministic). A
+ * quantile of slo_minutes is widened to int64. CCKA_EINVAL for a kind outside
+ * 0..2 or a non-SUM q_ppm outside [0, 1000000]. */
+int ccka_get_grid_stat(ccka_ctx* ctx, int64_t grid_size, const ccka_sweep_stat* stat, ccka_grid_stats* out,
+                       int64_t n_grids);
+/* ccka_pareto_frontier over those statistics (e.g. mean cost, mean gCO2, p95
+ * SLO minutes): the same dominance filter and exchange on the cost / gCO2 /
+ * SLO-minutes fields of ccka_get_grid_stat's rows. Grids shard whole, so no
+ * statistic crosses GPUs. */
+int ccka_pareto_frontier_stat(ccka_ctx* ctx, int64_t grid_size, const ccka_sweep_stat* stat, ccka_grid_stats* out,
+                              int32_t capacity, int32_t* n_out);
 
 /* ---- learned MLP control policy (BASELINE config 5) ------------------- */
 /* Weights of the state(64) -> 256 -> 256 -> actions(8) ReLU policy: bf16 bit
