@@ -60,8 +60,6 @@ static int sk_trace(ccka_ctx* c) {
   return CCKA_OK;
 }
 
-static int hist_entries(int window_s, int sync_s) { return window_s > sync_s ? (window_s - 1) / sync_s : 0; }
-
 static int plan_launch(ccka_ctx* c, KParams& k, int* block, size_t* lds) {
   const ccka_world& w = c->hw;
   const int B = 256;
@@ -114,11 +112,7 @@ int setup_general(ccka_ctx* c, int32_t trajectory, KParams& k, int* block_out, s
   if ((rc = plan_launch(c, k, &block, &lds)) != CCKA_OK) return rc;
   *block_out = block;
   *lds_out = lds;
-  const ResultPtrs& r = c->res;
-  k.cost = r.cost; k.energy = r.energy; k.gco2 = r.gco2; k.slo = r.slo; k.pend_min = r.pend_min;
-  k.nmin_spot = r.nmin_spot; k.nmin_od = r.nmin_od; k.launches = r.launches; k.deletions = r.deletions;
-  k.peak_nodes = r.peak_nodes; k.final_reps = r.final_reps; k.final_nodes = r.final_nodes;
-  k.last_choice = r.last_choice; k.hash = r.hash;
+  k.res = c->res;
   k.ablate = c->ablate;
   k.w = c->d_world;
   k.types = c->d_types;
@@ -189,7 +183,7 @@ int setup_general(ccka_ctx* c, int32_t trajectory, KParams& k, int* block_out, s
 // of two or more deployments that are HPA-scaled or static, with one HPA
 // decision per step over the register history rings, every hour's price tiles
 // in LDS, no detail breakdown and no drift / replacement / multi-node
-// consolidation (rollout.hip, rollout_kernel's SK notes).
+// consolidation (rollout_kernel.h, rollout_kernel's SK notes).
 static bool sk_eligible(const ccka_ctx* c, const KParams& k) {
   const ccka_world& w = c->hw;
   if (w.n_deploy < 2 || c->engine_mode == 2 || c->detail_on) return false;
@@ -231,10 +225,7 @@ int ccka_rollout_async(ccka_ctx* c, int32_t trajectory) {
     p.table = c->d_table; p.jtab = c->d_jtab;
     p.region = c->d_region; p.target = c->d_target; p.maxr = c->d_maxr; p.down_stab = c->d_dstab;
     p.reset_ca = c->d_resetca; p.pswitch = c->d_pswitch; p.wci = c->d_wci; p.cap_sel = c->d_capsel;
-    p.cost = k.cost; p.energy = k.energy; p.gco2 = k.gco2; p.slo = k.slo; p.pend_min = k.pend_min;
-    p.nmin_spot = k.nmin_spot; p.nmin_od = k.nmin_od; p.launches = k.launches; p.deletions = k.deletions;
-    p.peak_nodes = k.peak_nodes; p.final_reps = k.final_reps; p.final_nodes = k.final_nodes;
-    p.last_choice = k.last_choice; p.hash = k.hash; p.traj = k.traj;
+    p.res = k.res; p.traj = k.traj;
     p.N = c->N;
     p.NL = k.NL;
     p.trace_mod = k.trace_mod;
@@ -413,9 +404,7 @@ int ccka_get_totals(ccka_ctx* c, ccka_totals* out) {
   if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
   (void)hipSetDevice(c->device);
   TotParams q{};
-  const ResultPtrs& k = c->res;
-  q.cost = k.cost; q.energy = k.energy; q.gco2 = k.gco2; q.slo = k.slo; q.pend_min = k.pend_min;
-  q.nmin_spot = k.nmin_spot; q.nmin_od = k.nmin_od; q.launches = k.launches; q.deletions = k.deletions;
+  q.res = c->res;
   q.parts = (Part*)c->d_parts.get();
   q.ovf = c->d_parts + 1024 * 11;
   q.out = c->d_totals;

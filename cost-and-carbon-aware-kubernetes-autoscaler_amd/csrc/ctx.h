@@ -20,24 +20,6 @@
 // internal to libccka.so: nothing below is an exported symbol
 #pragma GCC visibility push(hidden)
 
-// the per-scenario result arrays, carved from one allocation (alloc_results)
-struct ResultPtrs {
-  int64_t* cost;
-  double* energy;
-  double* gco2;
-  int64_t* pend_min;
-  int32_t* slo;
-  int32_t* nmin_spot;
-  int32_t* nmin_od;
-  int32_t* launches;
-  int32_t* deletions;
-  int32_t* peak_nodes;
-  int32_t* final_reps;
-  int32_t* final_nodes;
-  uint32_t* last_choice;
-  uint32_t* hash;
-};
-
 struct ccka_ctx {
   template <class T>
   using Buf = ccka::DevBuf<T>;
@@ -81,7 +63,7 @@ struct ccka_ctx {
   int32_t load_nt_dp = 0;
   bool trace_flat = false;  // ccka_debug_trace_flat: read [T][N] (A/B of the layout)
   Buf<char> d_res;  // one allocation, SoA carve
-  ResultPtrs res{};
+  ccka::ResultPtrs res{};
   Buf<ccka_traj_rec> d_traj;  // [T][N] records (or [N][T]: traj_nt)
   bool traj_valid = false;
   bool traj_nt = false;          // device records are [N][T] (single-deployment engine)

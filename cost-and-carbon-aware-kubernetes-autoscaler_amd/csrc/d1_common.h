@@ -1,19 +1,17 @@
 // d1_common.h — device helpers of the single-deployment engine, rollout_d1.hip
-// (one wave per scenario batch, event steps per wave). Internal linkage: a
-// translation unit that includes it gets its own copy.
+// (one wave per scenario batch, event steps per wave); the leaf helpers every
+// kernel unit shares are dev_common.h's. Internal linkage: a translation unit
+// that includes it gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ccka.h"
+#include "dev_common.h"
 #include "kparams.h"
 
 namespace ccka {
 namespace {
-
-constexpr int WAVE = 64;
-
-__device__ __forceinline__ int capbit1(int c) { return c == 0 ? CCKA_CAP_SPOT : CCKA_CAP_OD; }
 
 // Opaque copy of a kernel argument: the value then lives in a register for the
 // whole loop (spilled to a VGPR lane if need be) instead of being re-read from
@@ -31,15 +29,6 @@ __device__ __forceinline__ GLOBAL_AS V* opq_ptr(V* v) {
   uint64_t x = (uint64_t)v;
   asm volatile("" : "+s"(x));
   return (GLOBAL_AS V*)x;
-}
-
-// down-window entries of a window (entry k is (k + 1) steps old): bit k set
-// while (k + 1) * 60 < window_s
-__device__ __forceinline__ int wmask(int window_s) {
-  int m = 0;
-#pragma unroll
-  for (int k = 0; k < CCKA_HIST; ++k) m |= ((k + 1) * CCKA_STEP_SECONDS < window_s) ? (1 << k) : 0;
-  return m;
 }
 
 // packed int16 history rings: entry k (k steps old, 0 = this step) sits in

@@ -1,6 +1,7 @@
 // kparams.h — kernel argument blocks shared by the kernel units and the C ABI (abi_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/ccka.h"
@@ -16,12 +17,36 @@ struct DetailDev {
 };
 
 // Words per scenario of the general kernel's persisted state block (the
-// closed loop): the st_xfer sequence of state_io in rollout.hip, one row per
+// closed loop): the st_xfer sequence of state_io in rollout_kernel.h, one row per
 // 32-bit value and two per 64-bit value. Host (allocation) and kernel (a
 // check folded away at compile time when the sequence matches) both use it.
 __host__ __device__ constexpr int64_t state_words(int dmax, int nmax) {
   return (int64_t)dmax * (5 + 2 * CCKA_HIST) + 5 * CCKA_MAX_POOLS + (int64_t)nmax * (6 + dmax) + 36;
 }
+
+// decision-history entries inside a window / period: entry k is (k + 1) * sync_s old
+__host__ __device__ constexpr int hist_entries(int window_s, int sync_s) {
+  return window_s > sync_s ? (window_s - 1) / sync_s : 0;
+}
+
+// the per-scenario result arrays, carved from one allocation (alloc_results):
+// every rollout kernel writes them, the totals kernels read them
+struct ResultPtrs {
+  int64_t* cost;
+  double* energy;
+  double* gco2;
+  int32_t* slo;
+  int64_t* pend_min;
+  int32_t* nmin_spot;
+  int32_t* nmin_od;
+  int32_t* launches;
+  int32_t* deletions;
+  int32_t* peak_nodes;
+  int32_t* final_reps;
+  int32_t* final_nodes;
+  uint32_t* last_choice;
+  uint32_t* hash;
+};
 
 constexpr int MLP_IN = 64, MLP_HID = 256, MLP_OUT = 8;
 typedef short mlp_bf16x8 __attribute__((ext_vector_type(8)));
@@ -53,21 +78,7 @@ struct KParams {
   const uint8_t* pswitch;
   const double* cw;
   const uint8_t* cap_sel;
-  // results
-  int64_t* cost;
-  double* energy;
-  double* gco2;
-  int32_t* slo;
-  int64_t* pend_min;
-  int32_t* nmin_spot;
-  int32_t* nmin_od;
-  int32_t* launches;
-  int32_t* deletions;
-  int32_t* peak_nodes;
-  int32_t* final_reps;
-  int32_t* final_nodes;
-  uint32_t* last_choice;
-  uint32_t* hash;
+  ResultPtrs res;
   ccka_traj_rec* traj;  // nullable
   DetailDev* detail;    // nullable: per-scenario summary breakdown (ccka_set_detail)
   int2* hist;           // HBM decision history [hlen][D][N] {rec + 1 (0: none), delta}; hlen 0: register rings
@@ -113,6 +124,7 @@ struct KParams {
   int32_t pNZI, pJT, pNW, _ppad2;
   int32_t pzmi[16];          // zone mask -> zone-mask index of the tables (-1: none)
 };
+static_assert(sizeof(KParams) == 656 && offsetof(KParams, traj) == 232, "KParams: the kernels' argument layout");
 
 struct GenParams {
   int32_t* out;
@@ -125,15 +137,7 @@ struct GenParams {
 
 struct Part;
 struct TotParams {
-  const int64_t* cost;
-  const double* energy;
-  const double* gco2;
-  const int32_t* slo;
-  const int64_t* pend_min;
-  const int32_t* nmin_spot;
-  const int32_t* nmin_od;
-  const int32_t* launches;
-  const int32_t* deletions;
+  ResultPtrs res;
   Part* parts;
   ccka_totals* out;
   long long* ovf;  // set when a fixed-point sum would leave int64
@@ -228,21 +232,7 @@ struct D1Params {
   const uint8_t* pswitch;
   const uint8_t* wci;        // carbon-weight index (NW distinct values)
   const uint8_t* cap_sel;
-  // results (same buffers as KParams)
-  int64_t* cost;
-  double* energy;
-  double* gco2;
-  int32_t* slo;
-  int64_t* pend_min;
-  int32_t* nmin_spot;
-  int32_t* nmin_od;
-  int32_t* launches;
-  int32_t* deletions;
-  int32_t* peak_nodes;
-  int32_t* final_reps;
-  int32_t* final_nodes;
-  uint32_t* last_choice;
-  uint32_t* hash;
+  ResultPtrs res;
   ccka_traj_rec* traj;  // nullable
   int64_t N;
   int64_t NL, trace_mod, first_id;  // load columns / shared-trace mapping (as KParams)
@@ -278,6 +268,7 @@ struct D1Params {
   int32_t k_min;   // minReplicaCount
   int32_t k_max;   // maxReplicaCount
 };
+static_assert(sizeof(D1Params) == 1048 && offsetof(D1Params, traj) == 232, "D1Params: the kernels' argument layout");
 
 // argmin-table builder: one wave per (region, hour, zone-mask, cap-mask, carbon weight)
 struct TableParams {

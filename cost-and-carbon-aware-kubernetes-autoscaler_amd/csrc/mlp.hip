@@ -27,57 +27,9 @@
 #include <stdint.h>
 
 #include "kparams.h"
+#include "mlp_dev.h"
 
 namespace ccka {
-
-namespace {
-
-typedef mlp_bf16x8 bf16x8;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int WAVE = 64;
-
-typedef short short2v __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-
-// registers 8s..8s+7 as one bf16 operand fragment with ReLU: pairs rounded to
-// nearest even (v_cvt_pk_bf16_f32), then ReLU on the bf16 bit patterns as
-// packed int16 max with 0 (v_pk_max_i16: every negative value, -0 included,
-// has the sign bit set) -- the same bits as rounding relu(x)
-__device__ __forceinline__ bf16x8 relu_pack(const f32x16& a, int s) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) {
-    const bf16x2v b = __builtin_convertvector((f32x2){a[8 * s + j], a[8 * s + j + 1]}, bf16x2v);
-    const short2v v = __builtin_elementwise_max(__builtin_bit_cast(short2v, b), (short2v){0, 0});
-    r[j] = v.x;
-    r[j + 1] = v.y;
-  }
-  return r;
-}
-
-// accumulator tile of the bias of rows 32 blocks: row = (reg&3) + 8(reg>>2) + 4h
-// (four 16-byte loads, L1/L2-resident; used as the C operand of the first MFMA)
-__device__ __forceinline__ f32x16 bias_tile(const float* b, int h) {
-  f32x16 a;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(b + 8 * g + 4 * h);
-    a[4 * g + 0] = v[0];
-    a[4 * g + 1] = v[1];
-    a[4 * g + 2] = v[2];
-    a[4 * g + 3] = v[3];
-  }
-  return a;
-}
-
-__device__ __forceinline__ f32x16 mfma(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-}  // namespace
 
 // One persistent 4-wave workgroup per CU. W1 fragments (32 KiB) live in each
 // wave's accumulation registers; W2 and W3 fragments and the biases
@@ -425,24 +377,11 @@ __global__ void __launch_bounds__(256, 1) mlp16_kernel(MlpParams p) {
 }
 
 // Synthetic cluster states: Irwin-Hall sums of Philox words (~N(0,1)), bf16.
-__device__ __forceinline__ void philox_s(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                         uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-  for (int q = 0; q < 10; ++q) {
-    const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-    const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __global__ void __launch_bounds__(256) mlp_gen_states_kernel(uint16_t* x, int64_t count, uint64_t seed) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= count) return;
   uint32_t u[4];
-  philox_s((uint32_t)e, (uint32_t)(e >> 32), 0x5EEDu, 0x57A7Eu, (uint32_t)seed, (uint32_t)(seed >> 32), u);
+  philox((uint32_t)e, (uint32_t)(e >> 32), 0x5EEDu, 0x57A7Eu, (uint32_t)seed, (uint32_t)(seed >> 32), u);
   const float v = ((float)(u[0] >> 16) + (float)(u[1] >> 16) + (float)(u[2] >> 16) + (float)(u[3] >> 16) - 131070.0f) *
                   (1.0f / 37837.0f);
   x[e] = __builtin_bit_cast(uint16_t, (__bf16)v);
@@ -455,18 +394,15 @@ hipError_t launch_mlp(const MlpParams& p, int cus, hipStream_t s) {
   return hipGetLastError();
 }
 
-// The policy's action -> this step's scaler parameters (SEMANTICS 5): the
-// HPA target utilisation 60 + rint(16 y0) clamped to [20, 95] %, and the
-// Karpenter carbon weight rint(16 y1) / 16 clamped to [0, 4] $/kgCO2. Scaling by
-// 16 is exact in fp32 and rint rounds half to even, so the mapping is
-// reproducible from y on any IEEE host.
+// The policy's action -> this step's scaler parameters (policy_action, mlp_dev.h)
 __global__ void __launch_bounds__(256) policy_act_kernel(const float* __restrict__ y, int16_t* target, double* cw,
                                                         int16_t* rec_target, double* rec_cw, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float q0 = rintf(y[i * 8 + 0] * 16.0f), q1 = rintf(y[i * 8 + 1] * 16.0f);
-  const int16_t tg = (int16_t)(60 + (int)fminf(fmaxf(q0, -40.0f), 35.0f));
-  const double c = (double)(int)fminf(fmaxf(q1, 0.0f), 64.0f) / 16.0;
+  int t;
+  double c;
+  policy_action(y[i * 8 + 0], y[i * 8 + 1], t, c);
+  const int16_t tg = (int16_t)t;
   target[i] = tg;
   cw[i] = c;
   if (rec_target) {

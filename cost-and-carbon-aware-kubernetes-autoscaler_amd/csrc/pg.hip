@@ -34,43 +34,17 @@
 #include <type_traits>
 
 #include "kparams.h"
+#include "mlp_dev.h"
 
 namespace ccka {
 
 namespace {
-
-typedef mlp_bf16x8 bf16x8;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short short2v __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-
-constexpr int WAVE = 64;
-
-__device__ __forceinline__ f32x16 mfma(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 
 __device__ __forceinline__ f32x16 zero16() {
   f32x16 z;
 #pragma unroll
   for (int k = 0; k < 16; ++k) z[k] = 0.f;
   return z;
-}
-
-// registers 8s..8s+7 -> bf16 (round to nearest even), then ReLU on the bits
-// (as mlp.hip's relu_pack: the forward's exact H1 / H2 operands)
-typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x8 relu_pack(const f32x16& a, int s) {
-  u32x4_ o;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const bf16x2v b = __builtin_convertvector((f32x2){a[8 * s + 2 * w], a[8 * s + 2 * w + 1]}, bf16x2v);
-    const short2v v = __builtin_elementwise_max(__builtin_bit_cast(short2v, b), (short2v){0, 0});
-    o[w] = __builtin_bit_cast(uint32_t, v);
-  }
-  return __builtin_bit_cast(bf16x8, o);
 }
 
 // registers 8s..8s+7 -> bf16, zeroed where the activation h is 0 (ReLU'(h) = 0),
@@ -96,20 +70,6 @@ __device__ __forceinline__ bf16x8 frag(__amdgpu_buffer_rsrc_t r, int lane16, int
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t frag_rsrc(const mlp_bf16x8* p, int nfrag) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, nfrag * WAVE * 16, 0x00020000);
 }
-
-__device__ __forceinline__ f32x16 bias_tile(const float* b, int h) {
-  f32x16 a;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(b + 8 * g + 4 * h);
-    a[4 * g + 0] = v[0];
-    a[4 * g + 1] = v[1];
-    a[4 * g + 2] = v[2];
-    a[4 * g + 3] = v[3];
-  }
-  return a;
-}
-
 
 // Row-blocked work arrays: element (unit u, row m) of a U-unit array sits at
 // ((m / 16) * U + u) * 16 + m % 16, so the 16 rows of a block are contiguous
@@ -168,58 +128,22 @@ __device__ __forceinline__ void store_rows(uint16_t* __restrict__ arr, int U, in
 __device__ __forceinline__ int o_kin(int j, int h) { return 8 * (j >> 2) + 4 * h + (j & 3); }
 __device__ __forceinline__ int o_lin(int j, int h) { return 8 * h + j; }
 
-__device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                       uint32_t out[4]) {
-#pragma unroll
-  for (int q = 0; q < 10; ++q) {
-    const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-    const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// Stochastic policy step (SEMANTICS 5): p = softmax(y) in binary32 (max
-// subtracted, expf); u = Philox(seed; global id, step) as a 24-bit uniform in
-// [0, 1); the action is the first a with u * sum(p) < p_0 + ... + p_a (the
-// last one if rounding leaves none). Action a maps to the HPA target
-// 40 + 10 (a & 3) % and the carbon weight (a >> 2) $/kgCO2.
+// Stochastic policy step (SEMANTICS 5): policy_sample and policy_bin_action,
+// mlp_dev.h.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) policy_sample_kernel(PgSampleParams q) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= q.n) return;
-  const float* y = q.y + i * MLP_OUT;
-  float p[MLP_OUT];
-  float mx = y[0];
-#pragma unroll
-  for (int a = 1; a < MLP_OUT; ++a) mx = fmaxf(mx, y[a]);
-  float sum = 0.f;
-#pragma unroll
-  for (int a = 0; a < MLP_OUT; ++a) {
-    p[a] = expf(y[a] - mx);
-    sum += p[a];
-  }
-  const int64_t g = q.first_id + i;
-  const uint64_t seed = *q.seed;
-  uint32_t u4[4];
-  philox((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)q.t, 0x5A3B1E7u, (uint32_t)seed, (uint32_t)(seed >> 32), u4);
-  const float u = (float)(u4[0] >> 8) * (1.0f / 16777216.0f) * sum;
-  int act = MLP_OUT - 1;  // the last action when rounding leaves u above every partial sum
-  float acc = 0.f;
-  bool found = false;
-#pragma unroll
-  for (int a = 0; a < MLP_OUT; ++a) {
-    acc += p[a];
-    if (!found && u < acc) { act = a; found = true; }
-  }
+  const int act = policy_sample(q.y + i * MLP_OUT, q.seed, q.first_id + i, q.t);
+  int tg;
+  double c;
+  policy_bin_action(act, tg, c);
   q.act[i] = (uint8_t)act;
-  q.target[i] = (int16_t)(40 + 10 * (act & 3));
-  q.cw[i] = (double)(act >> 2);
+  q.target[i] = (int16_t)tg;
+  q.cw[i] = c;
   if (q.rec_target) {
     q.rec_target[i] = q.target[i];
     q.rec_cw[i] = q.cw[i];
@@ -280,8 +204,8 @@ __global__ void __launch_bounds__(256, 1) pg_rows_kernel(PgRowsParams p) {
       f32x16 c = bias_tile(s_b + 32 * n, h);
 #pragma unroll
       for (int s = 0; s < KS1; ++s) c = mfma(wv[s], xf[s], c);
-      h1[2 * n] = relu_pack(c, 0);
-      h1[2 * n + 1] = relu_pack(c, 1);
+      h1[2 * n] = relu_pack_dw(c, 0);
+      h1[2 * n + 1] = relu_pack_dw(c, 1);
       __builtin_amdgcn_sched_barrier(0);
     }
     // ---- layer 2: H2^T = relu(bf16(W2^T H1^T + b2)); layer 3: Y^T = W3^T H2^T + b3 ----
@@ -299,8 +223,8 @@ __global__ void __launch_bounds__(256, 1) pg_rows_kernel(PgRowsParams p) {
       f32x16 c = bias_tile(s_b + MLP_HID + 32 * n, h);
 #pragma unroll
       for (int kk = 0; kk < KS2; ++kk) c = mfma(s_w2[(n * KS2 + kk) * WAVE + lane], h1[kk], c);
-      h2[2 * n] = relu_pack(c, 0);
-      h2[2 * n + 1] = relu_pack(c, 1);
+      h2[2 * n] = relu_pack_dw(c, 0);
+      h2[2 * n + 1] = relu_pack_dw(c, 1);
       yv = mfma(w30, h2[2 * n], yv);
       yv = mfma(w31, h2[2 * n + 1], yv);
       __builtin_amdgcn_sched_barrier(0);

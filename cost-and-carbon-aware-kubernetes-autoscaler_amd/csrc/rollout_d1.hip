@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(256) table_kernel(TableParams q) {
       for (int z = 0; z < q.Z; ++z) {
         if (!(zm >> z & 1u)) continue;
         for (int c = 0; c < 2; ++c) {
-          if (!(cm & (uint32_t)capbit1(c))) continue;
+          if (!(cm & (uint32_t)capbit(c))) continue;
           const int pr = tile[(k * q.Z + z) * 2 + c];
           if (pr <= 0) continue;
           const double score = (double)pr + wc * carbon;
@@ -361,8 +361,8 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
   const int mx = KEDA ? opq(p.k_max) : (p.maxr ? (int)p.maxr[i] : p.maxr0);
   const int dwin = (!KEDA && p.down_stab) ? (int)p.down_stab[i] : p.dstab0;
   // records inside the down window: entries k < (W - 1) / sync (o_entries)
-  const int nd = min(NSUB == 1 ? __popc(wmask(dwin)) : (dwin > 15 ? (dwin - 1) / 15 : 0), 2 * HW);
-  const int dnmask = NSUB == 1 ? wmask(dwin) : 0;
+  const int nd = min(NSUB == 1 ? __popc(window_mask(dwin)) : (dwin > 15 ? (dwin - 1) / 15 : 0), 2 * HW);
+  const int dnmask = NSUB == 1 ? window_mask(dwin) : 0;
   const int reset_ca = p.reset_ca ? (int)p.reset_ca[i] : p.reset_ca0;
   const int pswitch = p.pswitch ? (int)p.pswitch[i] : p.pswitch0;
   const int wi = p.wci ? (int)p.wci[i] : 0;
@@ -1012,7 +1012,7 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
 #pragma unroll
               for (int q = 0; q < MAXP; ++q)
                 if ((int)(x >> 13 & 3u) == q) { zm = pzi[q] >= 0 ? p.zml[pzi[q]] : 0u; cm = pcm[q]; }
-              const bool drifted = !(zm >> (x >> 10 & 3u) & 1u) || !(cm & capbit1((int)(x >> 12 & 1u)));
+              const bool drifted = !(zm >> (x >> 10 & 3u) & 1u) || !(cm & capbit((int)(x >> 12 & 1u)));
               dm |= ((used >> n & 1u) && drifted ? 1u : 0u) << n;
             }
             dmask = dm;
@@ -1147,7 +1147,7 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
                 }
                 const uint32_t bit = 1u << slot;
                 used |= bit;
-                if (capbit1(bc) & capsel) cmask |= bit;
+                if (capbit(bc) & capsel) cmask |= bit;
 #pragma unroll
                 for (int qq = 0; qq < MAXP; ++qq) if (qq == q) pmask[qq] |= bit;
                 placed += k;
@@ -1263,7 +1263,7 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
 #pragma unroll
                 for (int n = 0; n < MAXN; ++n)
                   if (n == m) { xm = sinfo[n]; sinfo[n] = xm & 0xFFFFu; capm = scap[n]; podm = spods[n]; }
-                const bool okc = (capbit1((int)(xm >> 12 & 1u)) & capsel) != 0;
+                const bool okc = (capbit((int)(xm >> 12 & 1u)) & capsel) != 0;
                 uint32_t sm = xm >> 16 & 0xFFu;
                 int got = 0;
                 while (sm) {
@@ -1364,7 +1364,7 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
                   }
                   const uint32_t bit = 1u << slot;
                   used |= bit;
-                  if (capbit1(bc) & capsel) cmask |= bit;
+                  if (capbit(bc) & capsel) cmask |= bit;
 #pragma unroll
                   for (int qq = 0; qq < MAXP; ++qq) if (qq == q) pmask[qq] |= bit;
                   if (delay == 0) rdy |= bit;
@@ -1607,7 +1607,7 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
                       }
                       const uint32_t bit = 1u << slot;
                       used |= bit;
-                      if (capbit1(bc) & capsel) cmask |= bit;
+                      if (capbit(bc) & capsel) cmask |= bit;
 #pragma unroll
                       for (int qq = 0; qq < MAXP; ++qq) if (qq == q) pmask[qq] |= bit;
                       if (delay == 0) rdy |= bit;
@@ -1689,7 +1689,7 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
                   }
                   const uint32_t bit = 1u << slot;
                   used |= bit;
-                  if (capbit1(bc) & capsel) cmask |= bit;
+                  if (capbit(bc) & capsel) cmask |= bit;
 #pragma unroll
                   for (int qq = 0; qq < MAXP; ++qq) if (qq == q) pmask[qq] |= bit;
                   if (delay == 0) rdy |= bit;
@@ -2000,74 +2000,20 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
   flush(T);
   energy_nw += e_hour;
   gco2 += (double)e_hour * (ci_min * 1e-9);
-  p.cost[i] = cost;
-  p.energy[i] = (double)energy_nw * 1e-9;
-  p.gco2[i] = gco2;
-  p.slo[i] = slo;
-  p.pend_min[i] = pend_min;
-  p.nmin_spot[i] = nmin_spot;
-  p.nmin_od[i] = nmin_od;
-  p.launches[i] = launches;
-  p.deletions[i] = deletions;
-  p.peak_nodes[i] = peak_nodes;
-  p.final_reps[i] = replicas;
-  p.final_nodes[i] = __popc(used);
-  p.last_choice[i] = last_choice;
-  p.hash[i] = hash;
-}
-
-// [N][T] -> [T][N] trajectory records (ccka_get_trajectory after the
-// single-deployment engine), steps [t0, t0 + tc) at a time into a bounded
-// staging buffer: 32 x 32 tiles through LDS, 16-byte elements, both sides
-// coalesced; the tiles are numbered on grid.x alone (no grid.y limit on N).
-__global__ void __launch_bounds__(256) traj_transpose_kernel(const int4* __restrict__ in, int4* __restrict__ out,
-                                                             int64_t N, int64_t T, int64_t t0, int64_t tc) {
-  __shared__ int4 tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  const int64_t ntn = (N + 31) / 32;
-  const int64_t tb = (int64_t)blockIdx.x / ntn * 32, n0 = (int64_t)blockIdx.x % ntn * 32;
-#pragma unroll
-  for (int k = 0; k < 32; k += 8) {
-    const int64_t n = n0 + ty + k, t = tb + tx;
-    if (n < N && t < tc) tile[ty + k][tx] = in[n * T + t0 + t];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 32; k += 8) {
-    const int64_t t = tb + ty + k, n = n0 + tx;
-    if (n < N && t < tc) out[t * N + n] = tile[tx][ty + k];
-  }
-}
-
-hipError_t launch_traj_transpose(const ccka_traj_rec* in, ccka_traj_rec* out, int64_t N, int64_t T, int64_t t0,
-                                 int64_t tc, hipStream_t s) {
-  const int64_t blocks = (N + 31) / 32 * ((tc + 31) / 32);
-  if (blocks <= 0) return hipSuccess;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(traj_transpose_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                     reinterpret_cast<const int4*>(in), reinterpret_cast<int4*>(out), N, T, t0, tc);
-  return hipGetLastError();
-}
-
-// [T][N] load trace -> wave-tiled [wave][T][lpw] (the single-deployment
-// kernels' read layout: a wave's rows contiguous, every row lpw wide, the last
-// wave's padded: one row stride for all), once per trace / lanes-per-wave
-// change (abi_rollout.cpp d1_trace_tile); reads coalesced, writes in runs of lpw ints.
-__global__ void __launch_bounds__(256) trace_tile_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out,
-                                                         int64_t N, int64_t T, int64_t lpw) {
-  const int64_t total = N * T, stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += stride) {
-    const int64_t t = x / N, n = x - t * N;
-    const int64_t w0 = n / lpw * lpw;
-    out[w0 * T + t * lpw + (n - w0)] = in[x];
-  }
-}
-
-hipError_t launch_trace_tile(const int32_t* in, int32_t* out, int64_t N, int64_t T, int32_t lpw, hipStream_t s) {
-  if (N <= 0 || T <= 0 || lpw <= 0) return hipErrorInvalidValue;
-  const int64_t b0 = (N * T + 255) / 256, blocks = b0 < 65536 ? b0 : 65536;
-  hipLaunchKernelGGL(trace_tile_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, out, N, T, (int64_t)lpw);
-  return hipGetLastError();
+  p.res.cost[i] = cost;
+  p.res.energy[i] = (double)energy_nw * 1e-9;
+  p.res.gco2[i] = gco2;
+  p.res.slo[i] = slo;
+  p.res.pend_min[i] = pend_min;
+  p.res.nmin_spot[i] = nmin_spot;
+  p.res.nmin_od[i] = nmin_od;
+  p.res.launches[i] = launches;
+  p.res.deletions[i] = deletions;
+  p.res.peak_nodes[i] = peak_nodes;
+  p.res.final_reps[i] = replicas;
+  p.res.final_nodes[i] = __popc(used);
+  p.res.last_choice[i] = last_choice;
+  p.res.hash[i] = hash;
 }
 
 hipError_t launch_table(const TableParams& t, hipStream_t s) {
@@ -2091,37 +2037,38 @@ hipError_t launch_rollout_d1(const D1Params& p, hipStream_t s) {
     q.lds_tab = 1;
     lds += tabB;
   }
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(B), lds, s, q); };
   // OCC = resident waves per SIMD the register allocation targets
   const bool d = p.bdef != 0;
   if (p.keda) {  // a KEDA ScaledObject: default behavior, one decision per step, no drift (d1_prepare)
-    if (p.he4) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true, false, 1, 4, false, true>), dim3(grid), dim3(B), lds, s, q);
-    else hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true, false, 1, 8, false, true>), dim3(grid), dim3(B), lds, s, q);
+    if (p.he4) go(rollout_d1_kernel<8, 2, false, 2, true, false, 1, 4, false, true>);
+    else go(rollout_d1_kernel<8, 2, false, 2, true, false, 1, 8, false, true>);
   } else if (p.nsub == 4) {  // 15 s HPA sync, default behavior (d1_check_world)
-    if (p.multi) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true, true, 4, 8, true>), dim3(grid), dim3(B), lds, s, q);
-    else if (p.drift) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true, true, 4>), dim3(grid), dim3(B), lds, s, q);
-    else hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true, false, 4>), dim3(grid), dim3(B), lds, s, q);
+    if (p.multi) go(rollout_d1_kernel<8, 2, false, 2, true, true, 4, 8, true>);
+    else if (p.drift) go(rollout_d1_kernel<8, 2, false, 2, true, true, 4>);
+    else go(rollout_d1_kernel<8, 2, false, 2, true, false, 4>);
   } else if (p.multi) {  // + multi-node consolidation (SEMANTICS 3.G3)
-    if (d) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true, true, 1, 8, true>), dim3(grid), dim3(B), lds, s, q);
-    else hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, false, true, 1, 8, true>), dim3(grid), dim3(B), lds, s, q);
+    if (d) go(rollout_d1_kernel<8, 2, false, 2, true, true, 1, 8, true>);
+    else go(rollout_d1_kernel<8, 2, false, 2, false, true, 1, 8, true>);
   } else if (p.drift) {  // drift (SEMANTICS 3.G0): 8 slots, <= 2 pools (d1_disrupt_ok)
-    if (d) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true, true>), dim3(grid), dim3(B), lds, s, q);
-    else hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, false, true>), dim3(grid), dim3(B), lds, s, q);
+    if (d) go(rollout_d1_kernel<8, 2, false, 2, true, true>);
+    else go(rollout_d1_kernel<8, 2, false, 2, false, true>);
   } else if (p.stamps) {
-    if (d && p.he4) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, true, 2, true, false, 1, 4>), dim3(grid), dim3(B), lds, s, q);
-    else if (d) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, true, 2, true>), dim3(grid), dim3(B), lds, s, q);
-    else hipLaunchKernelGGL((rollout_d1_kernel<8, 2, true, 2, false>), dim3(grid), dim3(B), lds, s, q);
+    if (d && p.he4) go(rollout_d1_kernel<8, 2, true, 2, true, false, 1, 4>);
+    else if (d) go(rollout_d1_kernel<8, 2, true, 2, true>);
+    else go(rollout_d1_kernel<8, 2, true, 2, false>);
   } else if (p.maxn <= 8 && p.NP <= 2 && p.occ == 3) {
-    hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 3, false>), dim3(grid), dim3(B), lds, s, q);
+    go(rollout_d1_kernel<8, 2, false, 3, false>);
   } else if (p.maxn <= 8 && p.NP <= 2) {
-    if (d && p.he4) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true, false, 1, 4>), dim3(grid), dim3(B), lds, s, q);
-    else if (d) hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, true>), dim3(grid), dim3(B), lds, s, q);
-    else hipLaunchKernelGGL((rollout_d1_kernel<8, 2, false, 2, false>), dim3(grid), dim3(B), lds, s, q);
+    if (d && p.he4) go(rollout_d1_kernel<8, 2, false, 2, true, false, 1, 4>);
+    else if (d) go(rollout_d1_kernel<8, 2, false, 2, true>);
+    else go(rollout_d1_kernel<8, 2, false, 2, false>);
   } else if (p.maxn <= 8) {
-    hipLaunchKernelGGL((rollout_d1_kernel<8, 4, false, 2, false>), dim3(grid), dim3(B), lds, s, q);
+    go(rollout_d1_kernel<8, 4, false, 2, false>);
   } else if (p.NP <= 2) {
-    hipLaunchKernelGGL((rollout_d1_kernel<16, 2, false, 1, false>), dim3(grid), dim3(B), lds, s, q);
+    go(rollout_d1_kernel<16, 2, false, 1, false>);
   } else {
-    hipLaunchKernelGGL((rollout_d1_kernel<16, 4, false, 1, false>), dim3(grid), dim3(B), lds, s, q);
+    go(rollout_d1_kernel<16, 4, false, 1, false>);
   }
   return hipGetLastError();
 }

@@ -1,9 +1,7 @@
 // rollout_multi.hip — the general kernel's lockstep instantiations for four or
-// more deployments (rollout_kernel<4|8|12|16, 8|16>). The kernel template is
-// rollout.hip's; this unit only instantiates it, so the instantiations compile
-// in parallel with rollout.hip's.
-#define CCKA_ROLLOUT_PART 1
-#include "rollout.hip"
+// more deployments (rollout_kernel<4|8|12|16, 8|16>, rollout_kernel.h), in a
+// unit of their own so that they compile in parallel with the other units'.
+#include "rollout_kernel.h"
 
 namespace ccka {
 

@@ -1,9 +1,7 @@
-// rollout_pol.hip — the fused closed loop's instantiations of rollout.hip's
-// kernel template (rollout_kernel<1, 8, POL>: features -> MFMA MLP -> action
-// -> step, the whole horizon in one launch), compiled in parallel with
-// rollout.hip.
-#define CCKA_ROLLOUT_PART 1
-#include "rollout.hip"
+// rollout_pol.hip — the fused closed loop's instantiations of the general
+// kernel template (rollout_kernel<1, 8, POL>, rollout_kernel.h: features ->
+// MFMA MLP -> action -> step, the whole horizon in one launch).
+#include "rollout_kernel.h"
 
 namespace ccka {
 

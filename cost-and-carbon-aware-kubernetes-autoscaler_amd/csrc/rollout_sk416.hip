@@ -1,12 +1,11 @@
 // rollout_sk416.hip — the lane-skewed schedule's four-deployment, 16-slot
-// instantiation (rollout_kernel<4, 16, 0, 1, 1>, rollout.hip), in its own unit:
+// instantiation (rollout_kernel<4, 16, 0, 1, 1>, rollout_kernel.h), in its own unit:
 // it is instantiated with the lane-local provisioning branch (LF2 = 1), which
 // never runs here (its per-lane NodeClaim columns, 180 KB, do not fit in LDS,
 // and the host enables it nowhere). With the branch present the register
 // allocator places this instantiation's spills off the hot loops: 214 -> 176 ms
 // at 1e5 x 1440 (bench --deployments 4, same results; tools/sk_ab.py).
-#define CCKA_ROLLOUT_PART 1
-#include "rollout.hip"
+#include "rollout_kernel.h"
 
 namespace ccka {
 

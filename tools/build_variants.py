@@ -1,14 +1,15 @@
-"""Build-time variants of the single-deployment kernel (D1_*_V macros in
-rollout_d1.hip: D1_S_V quiet steps per iteration, D1_K_V event cadence,
-D1_VMN_V trace rows in flight, D1_LEAN_V default-behavior quiet path, D1_NT_V /
-D1_NTL_V streaming hints) as separate libccka.so copies under csrc/build/variants/<name>/,
-linked with the main build's other objects. Profiling aid only.
-NAME=r@other.hip replaces rollout.hip (the general kernel) instead, NAME=p@other.hip pg.hip, NAME=m@other.hip
-mlp.hip (NAME=m@mlp.hip:-DX builds mlp.hip itself with extra flags), NAME=s@-DX rollout_sk.hip (the general
+"""Build-time variants of one kernel unit as separate libccka.so copies under
+csrc/build/variants/<name>/, linked with the main build's other objects. Profiling aid only.
+NAME=-DX builds rollout_d1.hip (the single-deployment engine) with extra flags, e.g.
+-DCCKA_ABLATE_BUILD=1 (kparams.h; tools/ablate.py). NAME=r@other.hip replaces rollout.hip (the general
+kernel's one- and two-deployment instantiations of rollout_kernel.h; NAME=r@rollout.hip:-DGK_STAMPS builds
+rollout.hip itself with the phase stamps), NAME=p@other.hip pg.hip, NAME=m@other.hip mlp.hip
+(NAME=m@mlp.hip:-DX builds mlp.hip itself with extra flags), NAME=s@-DX rollout_sk.hip (the general
 kernel's lane-skewed schedule; -DCCKA_SK_ONE instantiates <2, 8> only, -DCCKA_SK_LF2=1 instantiates its kernels
 with the lane-local provisioning branch, which the main build's abi_rollout.o then switches on). Set VARIANTS_NO_MAKE=1 to link
 against the objects already built.
-usage: python tools/build_variants.py name=-DD1_S_V=3 [name2="-DA -DB" ...]"""
+usage: python tools/build_variants.py name=-DCCKA_ABLATE_BUILD=1 [name2="-DA -DB" ...]"""
+import glob
 import os
 import subprocess
 import sys
@@ -40,10 +41,9 @@ for arg in sys.argv[1:]:
                                                     obj, os.path.join(CSRC, src)])))
 for name, out, obj, p in procs:
     assert p.wait() == 0, name
-    others = [os.path.join(CSRC, "build", f) for f in ("rollout.o", "rollout_multi.o", "rollout_pol.o", "rollout_sk.o",
-                                                       "rollout_sk416.o", "rollout_d1.o", "sweep.o", "mlp.o", "pg.o",
-                                                       "abi_ctx.o", "abi_rollout.o", "abi_policy.o", "abi_sweep.o",
-                                                       "abi_mlp.o", "abi_debug.o") if f != os.path.basename(obj)]
+    # the main build's other objects (the Makefile's UNITS and ABI_UNITS, as built)
+    others = [f for f in sorted(glob.glob(os.path.join(CSRC, "build", "*.o")))
+              if os.path.basename(f) != os.path.basename(obj)]
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o",
                     os.path.join(out, "libccka.so"), obj, *others, "-L/opt/rocm/lib", "-lrccl",
                     "-Wl,-rpath,/opt/rocm/lib"], check=True)
