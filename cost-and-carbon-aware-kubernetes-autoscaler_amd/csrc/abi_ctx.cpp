@@ -571,9 +571,12 @@ int ccka_set_scenarios(ccka_ctx* c, const ccka_scenarios* sc) {
   if (sc->cap_sel)
     for (size_t i = 0; i < n; ++i)
       if (sc->cap_sel[i] == 0 || sc->cap_sel[i] > 3) return fail(c, CCKA_EINVAL, "cap_sel invalid");
+  c->sc_target_max = -1;
   if (sc->target_util_pct)
-    for (size_t i = 0; i < n; ++i)
+    for (size_t i = 0; i < n; ++i) {
       if (sc->target_util_pct[i] <= 0) return fail(c, CCKA_EINVAL, "target_util_pct must be > 0");
+      c->sc_target_max = std::max<int>(c->sc_target_max, sc->target_util_pct[i]);
+    }
   c->sc_dstab_max = -1;
   if (sc->down_stab_s)
     for (size_t i = 0; i < n; ++i) {
@@ -602,9 +605,12 @@ int ccka_set_scenarios(ccka_ctx* c, const ccka_scenarios* sc) {
     for (size_t i = 0; i < n; ++i) c->sc_pswitch_any |= sc->peak_switch[i] != 0;
   }
   c->sc_maxr_ok = true;
+  c->sc_maxr_max = -1;
   if (sc->max_replicas)
-    for (size_t i = 0; i < n; ++i)
-      if (sc->max_replicas[i] < 0) { c->sc_maxr_ok = false; break; }
+    for (size_t i = 0; i < n; ++i) {
+      if (sc->max_replicas[i] < 0) c->sc_maxr_ok = false;
+      c->sc_maxr_max = std::max<int>(c->sc_maxr_max, sc->max_replicas[i]);
+    }
   c->d1_ready = false;
   c->N = sc->n;
   c->first_id = sc->first_id;

@@ -184,6 +184,7 @@ int setup_general(ccka_ctx* c, int32_t trajectory, KParams& k, int* block_out, s
 // decision per step over the register history rings, every hour's price tiles
 // in LDS, no detail breakdown and no drift / replacement / multi-node
 // consolidation (rollout_kernel.h, rollout_kernel's SK notes).
+constexpr int kSkMax16 = 32767;
 static bool sk_eligible(const ccka_ctx* c, const KParams& k) {
   const ccka_world& w = c->hw;
   if (w.n_deploy < 2 || c->engine_mode == 2 || c->detail_on) return false;
@@ -198,8 +199,18 @@ static bool sk_eligible(const ccka_ctx* c, const KParams& k) {
   for (int d = 0; d < w.n_deploy; ++d) {
     const int sc = w.deploy[d].scaler;
     if (sc != CCKA_SCALER_HPA && sc != CCKA_SCALER_STATIC) return false;
-    if (sc == CCKA_SCALER_HPA && w.deploy[d].target_util_pct <= 0) return false;
+    if (sc != CCKA_SCALER_HPA) continue;
+    // the quiet-step thresholds pack the tolerance band into 16-bit halves and
+    // multiply replicas by the target in 32 bits (rollout_kernel.h, q_band):
+    // targets and replica counts below 2^15, tolerance in [0, 1) as
+    // d1_check_world asks; anything else keeps the lockstep kernel
+    const ccka_deployment& dp = w.deploy[d];
+    if (dp.target_util_pct <= 0 || dp.target_util_pct > kSkMax16) return false;
+    if (!(dp.tolerance >= 0.0 && dp.tolerance < 1.0)) return false;
+    if (dp.max_replicas > kSkMax16 || dp.replicas0 > kSkMax16) return false;
   }
+  // the per-scenario overrides held in the context are bounded the same way
+  if (c->sc_target_max > kSkMax16 || c->sc_maxr_max > kSkMax16) return false;
   return true;
 }
 

@@ -81,6 +81,8 @@ struct ccka_ctx {
   bool d1_ok = false;        // world + scenarios qualify
   bool sc_maxr_ok = true;
   int sc_dstab_max = -1;      // largest per-scenario down_stab_s override (-1: none given)
+  int sc_target_max = -1;     // largest per-scenario target_util_pct override (-1: none given)
+  int sc_maxr_max = -1;       // largest per-scenario max_replicas override (-1: none given)
   // HPA decision history in HBM for long windows / sub-steps (general kernel)
   Buf<int2> d_hist;
   uint32_t sc_capsel_or = 0;  // OR of the per-scenario cap_sel overrides (0: none given)

@@ -163,11 +163,12 @@ __device__ int wave_launch(const Lds& L, int rl, uint32_t zm, uint32_t cm, int s
 }
 
 // 32-bit fast path of util = int32(usage*100 / (ready*req)) (exact: taken only
-// when both operands fit in 31 bits; the int64 divide is a long software
-// sequence on the GPU)
+// when both operands fit in 31 bits and the usage is not negative (a negative
+// load sample takes the signed division, C truncation as SEMANTICS 3.C; den
+// = pods x request > 0); the int64 divide is a long software sequence on the GPU)
 __device__ __forceinline__ int util_div(long long usage, long long den) {
   const long long num = usage * 100;
-  if (num < 0x7fffffffLL && den < 0x7fffffffLL) return (int)((unsigned)num / (unsigned)den);
+  if ((unsigned long long)num < 0x7fffffffULL && den < 0x7fffffffLL) return (int)((unsigned)num / (unsigned)den);
   return (int)(num / den);
 }
 
@@ -983,7 +984,7 @@ __global__ void __launch_bounds__(256, ((POL == 0 && DMAX == 1 && MAXN <= 8) || 
     return e;
   };
   // the quiet steps' caches after a full step at t (state final for the step)
-  auto sk_caches = [&](int t, bool peak) {
+  auto sk_caches = [&](int t, bool peak, bool launched) {
     int pend = 0, reps = 0;
     const bool unplaced = g_dirty;
     q_ran = 0;
@@ -1160,11 +1161,16 @@ __global__ void __launch_bounds__(256, ((POL == 0 && DMAX == 1 && MAXN <= 8) || 
       g_wake = gwk;
       nx = min(nx, gwk);
     }
-    if (unplaced) nx = t + 1;
-    if constexpr (kSKS) {
-      bool unpl = false;
+    // A step that launched a node and still left pods unplaced does not repeat
+    // itself: under NodePool limits a step's claims are sized against the pool
+    // usage at its start and launched against the current usage, so a later
+    // claim may be dropped while an earlier one's node has room left. The next
+    // step fills that room (E / F1) and sizes its claims against the new usage.
+    bool unpl = false;
 #pragma unroll
-      for (int d = 0; d < SKD; ++d) unpl = unpl || (d < D && placed[d] != replicas[d]);
+    for (int d = 0; d < SKD; ++d) unpl = unpl || (d < D && placed[d] != replicas[d]);
+    if (unplaced || (launched && unpl)) nx = t + 1;
+    if constexpr (kSKS) {
       // 1: pending pods (no longer a stall reason: counts full steps due to the rest while pods wait)
       sks_why = g_dirty ? 0 : nx == next_ready ? 3 : nx == t + 60 - mn % 60 ? 4 : unpl ? 1 : 2;
     }
@@ -1319,7 +1325,9 @@ __global__ void __launch_bounds__(256, ((POL == 0 && DMAX == 1 && MAXN <= 8) || 
         ci_gpwh = s_ci[(rl * 24 + h) * 2 + 1];
         base_price = (long long)base_nodes * tprice(L, rlx, base_type, 0, 1);
         burn = 0;
-        if (greplace) g_dirty = true;  // replacement offers depend on this hour's prices
+        // replacement offers (G2, and G3's one replacement against the sum of
+        // its candidates' prices) depend on this hour's prices
+        if (greplace || gmulti) g_dirty = true;
 #pragma unroll
         for (int n = 0; n < MAXN; ++n) {
           if (used >> n & 1u) {
@@ -1952,7 +1960,12 @@ __global__ void __launch_bounds__(256, ((POL == 0 && DMAX == 1 && MAXN <= 8) || 
     GK_STAMP(4);  // provisioning
     if (active) {
       // ---- G. disruption (skipped exactly when nothing it depends on moved) ----
-      const bool g_eval = (g_dirty || t >= g_wake) && !ablated(p.ablate, 1);
+      // With multi-node consolidation on, every step is evaluated: its prefix
+      // search succeeds or fails on the PDB allowance left by the step's other
+      // actions, and the skip missed a re-evaluation the step after a deletion
+      // (random world gk_multi seed 154: the consolidation came a step late).
+      // Evaluating is always exact; only the skip needs a proof.
+      const bool g_eval = (g_dirty || t >= g_wake || gmulti) && !ablated(p.ablate, 1);
       // One deployment without drift / replacement / multi-node consolidation:
       // an exact gate first (the single-deployment kernel's). The phase acts
       // only on a ready candidate past its consolidateAfter that is empty, or
@@ -2944,7 +2957,7 @@ __global__ void __launch_bounds__(256, ((POL == 0 && DMAX == 1 && MAXN <= 8) || 
     GK_STAMP(6);  // accounting, record
     if constexpr (SK) {
       if (active) {
-        sk_caches(t, (flags & 1u) != 0);
+        sk_caches(t, (flags & 1u) != 0, (flags & 2u) != 0);
         tl = t + 1;
         tq = tl;
         ev = false;
