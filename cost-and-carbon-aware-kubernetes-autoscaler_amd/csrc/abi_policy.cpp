@@ -275,6 +275,7 @@ static int pg_backward(ccka_ctx* c, const uint16_t* x, const uint8_t* act, const
   for (int64_t r0 = 0; r0 < M; r0 += CH) {
     const int64_t Mc = std::min(CH, M - r0);
     const int64_t Mpad = (Mc + 31) / 32 * 32;
+    c->pg_mpad = Mpad;
     uint16_t* xT = c->d_pg_work;
     uint16_t* h1T = xT + 64 * Mpad;
     uint16_t* h2T = h1T + MLP_HID * Mpad;
@@ -392,16 +393,20 @@ int ccka_policy_grad(ccka_ctx* c, const ccka_pg_params* pg, ccka_mlp_grads* out,
   return pg_copy_grads(c, out);
 }
 
-// Internal (tests): the backward's unit-major work arrays of the last
-// ccka_mlp_backward / ccka_policy_grad: xT | h1T | h2T | dh1T | dh2T | gyT,
-// each row-blocked [Mpad/16][units][16] bf16; *mpad receives Mpad.
+// Internal (tests): the backward's work arrays of the last ccka_mlp_backward /
+// ccka_policy_grad (its last row chunk): xT | h1T | h2T | dh1T | dh2T | gyT,
+// each row-blocked [Mpad/16][units][16] bf16, (64 + 4 * 256 + 8) * Mpad
+// elements; *mpad receives that backward's Mpad (the buffer itself only grows,
+// so its capacity does not locate the arrays after a smaller backward).
 int ccka_debug_pg_work(ccka_ctx* c, uint16_t* out, int64_t count, int64_t* mpad) {
-  if (!c || !out || !mpad || !c->d_pg_work) return CCKA_EINVAL;
+  if (!c || !out || !mpad || !c->d_pg_work || c->pg_mpad < 1) return CCKA_EINVAL;
   const int64_t rows = 64 + 4 * MLP_HID + 8;
-  const int64_t have = c->d_pg_work.count();  // grow-only: the largest backward's Mpad so far
+  const int64_t have = rows * c->pg_mpad;
+  if (have > c->d_pg_work.count()) return fail(c, CCKA_ESTATE, "work arrays released");
   if (count < have) return fail(c, CCKA_EINVAL, "need %lld", (long long)have);
   (void)hipSetDevice(c->device);
-  *mpad = have / rows;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *mpad = c->pg_mpad;
   HIPCHK(c, hipMemcpy(out, c->d_pg_work, (size_t)have * 2, hipMemcpyDeviceToHost));
   return CCKA_OK;
 }

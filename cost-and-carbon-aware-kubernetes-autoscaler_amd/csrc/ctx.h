@@ -151,6 +151,7 @@ struct ccka_ctx {
   bool pol_fused_off = false;  // ccka_debug_policy_fused(0): the launched loop even where the fused one applies
   bool pol_table_off = false;  // ccka_debug_policy_table(0): the fused loop's catalog scans instead of the tables
   int64_t pg_chunk = 0;        // ccka_debug_pg_chunk: rows per backward chunk (0: kPgChunkRows)
+  int64_t pg_mpad = 0;         // Mpad of the last backward's last chunk: what d_pg_work holds (ccka_debug_pg_work)
   Buf<int2> d_ptable;          // the fused loop's argmin tables (65 policy carbon weights)
   Buf<int32_t> d_pjtab;
   Buf<double> d_pwc;

@@ -4,7 +4,9 @@ from the scenario state. Parity is split where the arithmetic allows it:
 the features and the rollout under the recorded actions are bit-exact against
 the CPU oracle; the MLP itself is checked against a PyTorch fp32 reference
 (the actions derived from it agree except within rounding of an action
-boundary); the action mapping is reproduced in numpy."""
+boundary); the action mapping is reproduced in numpy, and every step's recorded
+actions equal that mapping of the standalone mlp_kernel's output on the step's
+features, for the fused and the launched loop."""
 import numpy as np
 import pytest
 
@@ -91,6 +93,42 @@ def test_closed_loop_policy_parity(engine, drift):
         ok = (want_t == at[t]) & (want_c == ac[t])
         assert (ok | near).all(), f"step {t}: {np.count_nonzero(~(ok | near))} actions off"
         assert ok.mean() > 0.98
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("loop", ["fused", "launched"])
+def test_closed_loop_actions_are_the_standalone_mlp(engine, loop):
+    """Every step of a recorded loop (512 scenarios x 60 steps): the step's
+    features through the standalone mlp_kernel (tile 32) and the action mapping
+    restated in numpy give the recorded (target, carbon weight) of every
+    scenario, with equality. The launched loop runs that kernel itself; the
+    fused loop's in-kernel MLP reproduces it bit for bit, and the mapping is
+    exact from y, so no rounding-boundary allowance applies."""
+    import ctypes as C
+    from test_gpu_mlp import run_forward
+    spec, sc, load = _case(n=512, T=60)
+    ws, bs = configs.mlp_weights(11)
+    engine.set_world(spec)
+    engine.set_scenarios(sc)
+    engine.set_load(load)
+    engine.mlp_set_weights([configs.to_bf16_bits(w) for w in ws], bs)
+    fu = engine.lib.ccka_debug_policy_fused
+    fu.argtypes = [C.c_void_p, C.c_int32]
+    engine.debug_policy_features(True)
+    try:
+        assert fu(engine.ctx, 1 if loop == "fused" else 0) == 0
+        engine.policy_rollout(trajectory=False, record=True)
+        at, ac = engine.policy_actions()
+        fg = engine.debug_get_policy_features()
+    finally:
+        fu(engine.ctx, 1)
+        engine.debug_policy_features(False)
+    assert engine.last_engine()[0] == (4 if loop == "fused" else 3)
+    assert at.std() > 0 and len(np.unique(at)) >= 3  # the policy really steers
+    for t in range(spec.n_steps):
+        want_t, want_c = po.policy_act(run_forward(engine, fg[t], 32))
+        bad = np.nonzero((want_t != at[t]) | (want_c != ac[t]))[0]
+        assert bad.size == 0, f"step {t}: {bad.size} actions differ, scenarios {bad[:8].tolist()}"
 
 
 @pytest.mark.gpu

@@ -4,7 +4,8 @@ NAME=-DX builds rollout_d1.hip (the single-deployment engine) with extra flags, 
 -DCCKA_ABLATE_BUILD=1 (kparams.h; tools/ablate.py). NAME=r@other.hip replaces rollout.hip (the general
 kernel's one- and two-deployment instantiations of rollout_kernel.h; NAME=r@rollout.hip:-DGK_STAMPS builds
 rollout.hip itself with the phase stamps), NAME=p@other.hip pg.hip, NAME=m@other.hip mlp.hip
-(NAME=m@mlp.hip:-DX builds mlp.hip itself with extra flags), NAME=s@-DX rollout_sk.hip (the general
+(NAME=m@mlp.hip:-DX builds mlp.hip itself with extra flags), NAME=a@other.cpp abi_mlp.cpp (the weight
+packing; mutation checks of tests/test_gpu_mlp.py and tests/test_gpu_pg.py), NAME=s@-DX rollout_sk.hip (the general
 kernel's lane-skewed schedule; -DCCKA_SK_ONE instantiates <2, 8> only, -DCCKA_SK_LF2=1 instantiates its kernels
 with the lane-local provisioning branch, which the main build's abi_rollout.o then switches on). Set VARIANTS_NO_MAKE=1 to link
 against the objects already built.
@@ -32,6 +33,8 @@ for arg in sys.argv[1:]:
         defs, src, base, extra = defs[2:], "rollout_sk.hip", "rollout_sk.o", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
     elif defs.startswith("m@"):  # the MLP kernels' source
         defs, base, extra = defs[1:], "mlp.o", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+    elif defs.startswith("a@"):  # the MLP's host side (weight fragment packing), e.g. a mutated copy elsewhere
+        defs, base, extra = defs[1:], "abi_mlp.o", ["-I", CSRC]
     if defs.startswith("@"):  # NAME=@other.hip[:flags]: another source file in csrc/ (e.g. a committed version)
         src, _, defs = defs[1:].partition(":")
     out = os.path.join(CSRC, "build", "variants", name)

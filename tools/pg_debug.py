@@ -1,5 +1,6 @@
-"""Diagnostic: the policy-gradient backward's intermediate unit-major arrays
-against PyTorch (which stage disagrees). Profiling/debug aid only."""
+"""Diagnostic: the policy-gradient backward's intermediate work arrays
+(row-blocked; tests/mlp_ref.py decode_work) against PyTorch (which stage
+disagrees). Profiling/debug aid only."""
 import ctypes as C
 import os
 import sys
@@ -13,6 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 from ccka import configs  # noqa: E402
 from ccka.engine import Engine  # noqa: E402
+import mlp_ref  # noqa: E402
 from test_gpu_pg import rel_err, torch_grads  # noqa: E402
 
 eng = Engine(0)
@@ -27,9 +29,7 @@ for m in (1, 40, 5000):
     got = eng.mlp_backward(x, act, coef)
     want = torch_grads(x, act, coef, wb, bs)
     print(m, {k: round(rel_err(got[k], want[k]), 4) for k in want}, flush=True)
-    rows = 64 + 4 * 256 + 9
-    mp_guess = (m + 31) // 32 * 32
-    buf = np.zeros(rows * mp_guess + 64, np.uint16)
+    buf = np.zeros(mlp_ref.WORK_ROWS * mlp_ref.mpad(m), np.uint16)
     mp = C.c_int64()
     fn = eng.lib.ccka_debug_pg_work
     fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
@@ -37,10 +37,10 @@ for m in (1, 40, 5000):
     if rc:
         print("work fetch rc", rc)
         continue
-    Mp = mp.value
-    wk = buf[:rows * Mp].reshape(rows, Mp)
+    # row-blocked [Mpad/16][units][16] (pg.hip, rb_off) -> [units][rows] as the code below reads them
+    wk = mlp_ref.decode_work(buf, mp.value)
     f = lambda a: configs.from_bf16_bits(a)  # noqa: E731
-    xT, h1T, h2T, dh1T, dh2T, gyT = (wk[0:64], wk[64:320], wk[320:576], wk[576:832], wk[832:1088], wk[1088:1096])
+    xT, h1T, h2T, dh1T, dh2T, gyT = (wk[k].T for k in ("x", "h1", "h2", "dh1", "dh2", "g"))
     xf = torch.from_numpy(f(x))
     W = [torch.from_numpy(f(w)) for w in wb]
     B = [torch.from_numpy(b) for b in bs]
