@@ -322,6 +322,21 @@ class Engine:
                   "ccka_debug_last_engine")
         return e.value, ms.value
 
+    PLAN_FIELDS = ("grid", "span", "all_hours", "hlen", "lds", "lclaims", "trace_mod",
+                   "lds_tab", "nw", "nzi", "jt", "inst")
+
+    def last_plan(self) -> dict:
+        """Internal: the launch plan of the last rollout (ccka_debug_last_plan):
+        workgroups, the general kernel's span / all_hours / hlen, dynamic LDS
+        bytes, lane-local provisioning, shared traces, and the single-deployment
+        kernel's lds_tab, NW, NZI, JT and instantiation (slots * 100 + pools);
+        -1 where a field does not apply to the engine that ran."""
+        fn = self.lib.ccka_debug_last_plan
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        out = (C.c_int32 * 12)()
+        self._chk(fn(self.ctx, out), "ccka_debug_last_plan")
+        return dict(zip(self.PLAN_FIELDS, out))
+
     def device_info(self):
         name = C.create_string_buffer(256)
         cus = C.c_int32()

@@ -81,6 +81,21 @@ int ccka_debug_last_engine(ccka_ctx* c, int32_t* engine, double* table_ms) {
   return CCKA_OK;
 }
 
+// Internal: the launch plan of the last whole-horizon rollout
+// (ccka_rollout / ccka_rollout_async), in kparams.h PlanField order:
+// workgroups, span, all_hours, hlen, dynamic LDS bytes, lane-local
+// provisioning, shared traces, then the single-deployment kernel's lds_tab,
+// NW, NZI, JT and instantiation (slots * 100 + pools). -1 = the field does not
+// apply to the engine that ran. The closed loops record none (CCKA_ESTATE).
+// Reads state only.
+int ccka_debug_last_plan(ccka_ctx* c, int32_t out[12]) {
+  static_assert(PLAN_FIELDS == 12, "ccka_debug_last_plan's out[12]");
+  if (!c || !out) return CCKA_EINVAL;
+  if (!c->ran || c->last_engine == 3 || c->last_engine == 4) return fail(c, CCKA_ESTATE, "no whole-horizon rollout ran last");
+  std::copy(c->last_plan, c->last_plan + PLAN_FIELDS, out);
+  return CCKA_OK;
+}
+
 // Internal: rows per policy-gradient backward chunk (0 = the default 2^23), to
 // exercise the chunked sum at test sizes. Any row count: a chunk that is no
 // multiple of the 32-row tile ends in padding rows like the last one does.

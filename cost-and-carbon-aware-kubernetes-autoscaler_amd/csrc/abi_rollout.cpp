@@ -227,6 +227,9 @@ int ccka_rollout_async(ccka_ctx* c, int32_t trajectory) {
   int rc;
   KParams k;
   if ((rc = setup_general(c, trajectory, k, &block, &lds)) != CCKA_OK) return rc;
+  int32_t* const plan = c->last_plan;  // recorded for ccka_debug_last_plan, read by nothing here
+  std::fill(plan, plan + PLAN_FIELDS, -1);
+  plan[PLAN_TRACE_MOD] = k.trace_mod != 0;
   if (c->engine_mode == 0 && c->d1_world && !c->d1_ready && (rc = d1_prepare(c)) != CCKA_OK) return rc;
   if (c->engine_mode == 0 && c->d1_world && c->d1_ok && !c->detail_on) {
     // single-deployment engine: argmin tables for this rollout, then the rollout
@@ -264,7 +267,10 @@ int ccka_rollout_async(ccka_ctx* c, int32_t trajectory) {
       p.table2 = c->d_table2;
     }
     HIPCHK(c, hipEventRecord(c->ev_mid, c->stream));
-    HIPCHK(c, launch_rollout_d1(p, c->stream));
+    HIPCHK(c, launch_rollout_d1(p, c->stream, plan));
+    plan[PLAN_D1_NW] = c->NW;
+    plan[PLAN_D1_NZI] = p.NZI;
+    plan[PLAN_D1_JT] = p.JT;
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->last_engine = 2;
     c->traj_nt = true;
@@ -291,6 +297,14 @@ int ccka_rollout_async(ccka_ctx* c, int32_t trajectory) {
     if (sk) HIPCHK(c, launch_rollout_sk(k, block, lds, c->stream));
     else HIPCHK(c, launch_rollout(k, block, lds, c->stream));
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    // (a copy of the general launchers' one-line grid rule, not read back from
+    // them: one scenario per thread, launch_rollout / _multi / _sk / _sk416)
+    plan[PLAN_GRID] = (int32_t)((c->N + block - 1) / block);
+    plan[PLAN_SPAN] = k.span;
+    plan[PLAN_ALL_HOURS] = k.all_hours;
+    plan[PLAN_HLEN] = k.hlen;
+    plan[PLAN_LDS] = (int32_t)lds;
+    plan[PLAN_LCLAIMS] = k.lds_lclaims >= 0;
     c->last_engine = sk ? 5 : 1;
     c->traj_nt = sk;  // the skewed schedule writes scenario-major records
   }

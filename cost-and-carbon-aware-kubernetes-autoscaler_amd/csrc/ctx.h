@@ -135,6 +135,10 @@ struct ccka_ctx {
   Buf<float> d_my;
   int64_t mlp_n = 0;
   int last_engine = 0;       // 1 general, 2 single-deployment
+  // launch plan of the last ccka_rollout_async (ccka_debug_last_plan): what
+  // plan_launch, the engine choice and launch_rollout_d1 decided; -1 = the
+  // field does not apply to the engine that ran. Recorded only, never read back.
+  int32_t last_plan[ccka::PLAN_FIELDS] = {0};
   // closed-loop policy rollout (config 5)
   Buf<int32_t> d_pol_state;
   Buf<int16_t> d_pol_target;

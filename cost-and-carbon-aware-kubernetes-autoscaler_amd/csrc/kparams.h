@@ -342,7 +342,25 @@ hipError_t launch_mlp_gen_states(uint16_t* x, int64_t count, uint64_t seed, hipS
 // policy actions -> the step's scaler parameters (SEMANTICS 5); rec_* nullable
 hipError_t launch_policy_act(const float* y, int16_t* target, double* cw, int16_t* rec_target, double* rec_cw,
                              int64_t n, hipStream_t s);
-hipError_t launch_rollout_d1(const D1Params& p, hipStream_t s);
+// The launch plan a rollout records for ccka_debug_last_plan (abi_debug.cpp):
+// fields in the order of its out[12]; -1 where a field does not apply.
+enum PlanField {
+  PLAN_GRID = 0,     // workgroups launched
+  PLAN_SPAN,         // general kernel: regions staged per block
+  PLAN_ALL_HOURS,    // general kernel: all 24 hourly tiles staged (no restage barrier)
+  PLAN_HLEN,         // general kernel: HBM history entries (0: register rings)
+  PLAN_LDS,          // dynamic LDS bytes of the launch
+  PLAN_LCLAIMS,      // skewed schedule: lane-local provisioning (lds_lclaims >= 0)
+  PLAN_TRACE_MOD,    // shared traces (trace_mod != 0)
+  PLAN_D1_LDS_TAB,   // single-deployment kernel: price tiles, ci and J in LDS
+  PLAN_D1_NW,        //   distinct carbon weights
+  PLAN_D1_NZI,       //   distinct zone masks
+  PLAN_D1_JT,        //   argmin-table entries per key
+  PLAN_D1_INST,      //   instantiation: slots * 100 + pools of its template pair
+  PLAN_FIELDS
+};
+// plan (nullable): PLAN_GRID, PLAN_LDS, PLAN_D1_LDS_TAB and PLAN_D1_INST of the launch
+hipError_t launch_rollout_d1(const D1Params& p, hipStream_t s, int32_t* plan = nullptr);
 
 // ---------------------------------------------------------------------------
 // Differentiable control: score-function policy gradient (pg.hip)

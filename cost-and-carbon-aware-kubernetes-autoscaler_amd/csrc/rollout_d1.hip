@@ -2023,7 +2023,7 @@ hipError_t launch_table(const TableParams& t, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_rollout_d1(const D1Params& p, hipStream_t s) {
+hipError_t launch_rollout_d1(const D1Params& p, hipStream_t s, int32_t* plan) {
   const int B = 256;
   const int64_t waves = (p.N + p.lpw - 1) / p.lpw;
   const unsigned grid = (unsigned)((waves + B / WAVE - 1) / (B / WAVE));
@@ -2040,6 +2040,7 @@ hipError_t launch_rollout_d1(const D1Params& p, hipStream_t s) {
   auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(B), lds, s, q); };
   // OCC = resident waves per SIMD the register allocation targets
   const bool d = p.bdef != 0;
+  int inst = 802;  // the (slots, pools) template pair chosen below, for the plan
   if (p.keda) {  // a KEDA ScaledObject: default behavior, one decision per step, no drift (d1_prepare)
     if (p.he4) go(rollout_d1_kernel<8, 2, false, 2, true, false, 1, 4, false, true>);
     else go(rollout_d1_kernel<8, 2, false, 2, true, false, 1, 8, false, true>);
@@ -2064,11 +2065,20 @@ hipError_t launch_rollout_d1(const D1Params& p, hipStream_t s) {
     else if (d) go(rollout_d1_kernel<8, 2, false, 2, true>);
     else go(rollout_d1_kernel<8, 2, false, 2, false>);
   } else if (p.maxn <= 8) {
+    inst = 804;
     go(rollout_d1_kernel<8, 4, false, 2, false>);
   } else if (p.NP <= 2) {
+    inst = 1602;
     go(rollout_d1_kernel<16, 2, false, 1, false>);
   } else {
+    inst = 1604;
     go(rollout_d1_kernel<16, 4, false, 1, false>);
+  }
+  if (plan) {
+    plan[PLAN_GRID] = (int32_t)grid;
+    plan[PLAN_LDS] = (int32_t)lds;
+    plan[PLAN_D1_LDS_TAB] = q.lds_tab;
+    plan[PLAN_D1_INST] = inst;
   }
   return hipGetLastError();
 }

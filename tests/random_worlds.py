@@ -19,6 +19,12 @@ constant burst load (levels 0, hi/8, hi/2, hi held 10-40 steps, 5 % noise;
 in one world of four 1 % of the samples are -5000, 2e9 or 2^31 - 1).
 The worlds are tuned for activity (launches, deletions, drift, replacement):
 tests/test_random_worlds.py holds the floors.
+
+The wide profiles (WIDE_PROFILES, 100 worlds each) leave that shape on purpose:
+catalogs of 63-200 types, 1-8 regions laid out over three workgroups of 600
+scenarios, 3-4 pools, 9-16 slots, shared traces, 8 carbon weights / zone
+masks. Their sub-kinds are chosen by the seed (seed % 3, seed % 4, ...), so
+how many worlds take each kernel path is fixed, not a matter of luck.
 """
 from __future__ import annotations
 
@@ -44,7 +50,27 @@ PROFILES = {
     "sk": 5,           # 2-4 HPA / static deployments on the lane-skewed schedule
     "loop": 4,         # closed-loop worlds (fused loop; 3 when the fused loop is switched off)
 }
-_PIDX = {p: i for i, p in enumerate(PROFILES)}
+# the wide profiles (100 worlds each): catalogs of 63-200 types, 3-8 regions,
+# 600 scenarios in three workgroups, shared traces, the slot / pool limits
+WIDE_PROFILES = {
+    "d1_wide": 2,      # one HPA deployment: 3-4 pools, 9-16 slots, 63-200 types, up to 8 weights / zone masks
+    "gk_wide": 1,      # gk_single / gk_multi worlds, 600 scenarios over 3-8 regions, 65-200 types
+    "sk_wide": 5,      # sk worlds, 600 scenarios over 3-8 regions, 64-130 types, 8 / 16 slots
+}
+WIDE_SEEDS = 100
+_PIDX = {p: i for i, p in enumerate(list(PROFILES) + list(WIDE_PROFILES))}
+
+
+def pod_cap1(spec):
+    """Pod capacity per type for deployment 0 (abi_ctx.cpp pod_cap, floored at 0)."""
+    ac, am = spec.catalog.alloc()
+    d = spec.deploys[0]
+    cap = spec.catalog.max_pods.astype(np.int64)
+    if d.req_cpu_m > 0:
+        cap = np.minimum(cap, ac // d.req_cpu_m)
+    if d.req_mem_mi > 0:
+        cap = np.minimum(cap, am // d.req_mem_mi)
+    return np.maximum(cap, 0)
 
 
 def pick(rng, seq):
@@ -116,7 +142,7 @@ def _pools(rng, Z, n_pools, disrupt=False, limits=False):
             p.profile[abi.PROFILE_RESET] = patch(pick(rng, [0, WEOU]), pick(rng, [-1, 0, 30]), 0, 0)
             zo = _mask(rng, Z)
             zp = _mask(rng, Z)
-            while zp == zo:
+            while zp == zo and Z > 1:  # (one zone: both profiles name it)
                 zp = _mask(rng, Z)
             if rng.integers(2) and (zo & ~zp):  # disjoint: every node of the old profile drifts
                 zo &= ~zp
@@ -185,8 +211,7 @@ def _timing(rng):
     return (T, start, edge, other) if rng.integers(2) else (T, start, other, edge)
 
 
-def _scenarios(rng, R, stab_set, cap_set=(1, 2, 3), switch_p=0.85):
-    n = N_SCEN
+def _scenarios(rng, R, stab_set, cap_set=(1, 2, 3), switch_p=0.85, n=N_SCEN):
     kw = {}
     if rng.random() < 0.6:
         kw["target_util_pct"] = rng.integers(30, 96, size=n).astype(np.int16)
@@ -208,9 +233,9 @@ def _scenarios(rng, R, stab_set, cap_set=(1, 2, 3), switch_p=0.85):
     return ScenarioSet(n, int(rng.integers(0, 1001)), **kw)
 
 
-def _load(rng, T, his):
+def _load(rng, T, his, n=N_SCEN):
     """[T][D][n] piecewise-constant bursts, one column per (deployment, scenario)."""
-    D, n = len(his), N_SCEN
+    D = len(his)
     S = T // 10 + 1
     ends = np.cumsum(rng.integers(10, 41, size=(D, n, S)), axis=2)
     seg = (ends[None] <= np.arange(T)[:, None, None, None]).sum(axis=3)          # [T][D][n]
@@ -227,7 +252,8 @@ def _load(rng, T, his):
 
 def _world(rng, deploys, pools, cat, R, Z, max_nodes, **kw):
     T, start, ps, pe = _timing(rng)
-    return WorldSpec(catalog=cat, ci=rng.uniform(50.0, 700.0, size=(R, 24)), price=_prices(rng, cat, R, Z),
+    prices = _prices_wide if cat.k > 6 else _prices
+    return WorldSpec(catalog=cat, ci=rng.uniform(50.0, 700.0, size=(R, 24)), price=prices(rng, cat, R, Z),
                      pools=pools, deploys=deploys, n_steps=T, start_minute=start,
                      provision_delay_steps=pick(rng, [0, 1, 1, 1, 2, 3]), max_nodes=max_nodes,
                      base_nodes=int(rng.integers(0, 4)), base_util=pick(rng, [0.0, 0.25]),
@@ -246,7 +272,7 @@ HIS = [3000, 9000, 20000]
 # ---------------------------------------------------------------------------
 # profiles
 # ---------------------------------------------------------------------------
-def _d1(rng, kind):
+def _d1(rng, kind, n=N_SCEN):
     cat, R, Z = _geo(rng)
     hi = pick(rng, HIS)
     kw = {}
@@ -272,12 +298,12 @@ def _d1(rng, kind):
         kw.update(drift=on & 1, replace=(on >> 1) & 1, multi=(on >> 2) & 1)
     pools = _pools(rng, Z, int(rng.integers(1, 3)), disrupt=disrupt)
     spec = _world(rng, [dep], pools, cat, R, Z, int(rng.integers(3, 9)), **kw)
-    sc = _scenarios(rng, R, stab_set, cap_set, switch_p=0.95 if disrupt else 0.85)
-    return spec, sc, _load(rng, spec.n_steps, [hi])
+    sc = _scenarios(rng, R, stab_set, cap_set, switch_p=0.95 if disrupt else 0.85, n=n)
+    return spec, sc, _load(rng, spec.n_steps, [hi], n)
 
 
-def _gk_single(rng):
-    cat, R, Z = _geo(rng)
+def _gk_single(rng, geo=None, n=N_SCEN):
+    cat, R, Z = geo or _geo(rng)
     hi = pick(rng, HIS)
     why = pick(rng, ["pool_limit", "slots_drift", "policies3", "window", "sync30"])
     kw = {}
@@ -306,14 +332,14 @@ def _gk_single(rng):
     disrupt = bool(kw.get("drift") or kw.get("replace") or kw.get("multi"))
     pools = _pools(rng, Z, int(rng.integers(1, 4)), disrupt=disrupt, limits=why == "pool_limit")
     spec = _world(rng, [dep], pools, cat, R, Z, slots, **kw)
-    sc = _scenarios(rng, R, stab_set)
+    sc = _scenarios(rng, R, stab_set, n=n)
     if why == "slots_drift" and sc.peak_switch is not None:
         sc.peak_switch[0] = 1  # one switching scenario: drift is not inert
-    return spec, sc, _load(rng, spec.n_steps, [hi])
+    return spec, sc, _load(rng, spec.n_steps, [hi], n)
 
 
-def _gk_multi(rng):
-    cat, R, Z = _geo(rng)
+def _gk_multi(rng, geo=None, n=N_SCEN):
+    cat, R, Z = geo or _geo(rng)
     on = int(rng.integers(0, 8))
     kw = dict(drift=on & 1, replace=(on >> 1) & 1, multi=(on >> 2) & 1)
     disrupt = on != 0
@@ -342,25 +368,252 @@ def _gk_multi(rng):
                 his.append(hi)
     pools = _pools(rng, Z, int(rng.integers(1, 4)), disrupt=disrupt, limits=rng.integers(3) == 0)
     spec = _world(rng, deploys, pools, cat, R, Z, int(rng.integers(8, 17)), **kw)
-    sc = _scenarios(rng, R, (0, 60, 300, 480), (2, 3, 3) if disrupt else (1, 2, 3), switch_p=0.95 if disrupt else 0.85)
-    return spec, sc, _load(rng, spec.n_steps, his)
+    sc = _scenarios(rng, R, (0, 60, 300, 480), (2, 3, 3) if disrupt else (1, 2, 3), switch_p=0.95 if disrupt else 0.85,
+                    n=n)
+    return spec, sc, _load(rng, spec.n_steps, his, n)
 
 
-def _sk(rng):
-    cat, R, Z = _geo(rng)
+def _sk(rng, geo=None, n=N_SCEN, slots=None):
+    cat, R, Z = geo or _geo(rng)
     n_dep = int(rng.integers(2, 5))
     kinds = ["hpa", "hpa"] + [pick(rng, ["hpa", "static"]) for _ in range(n_dep - 2)]
     deploys = [_hpa(rng, rules=pick(rng, ["default", "ring"]), stab_set=(0, 60, 300, 480), tol_set=(0.1, 0.0, 0.25, 0.05))
                if k == "hpa" else _static(rng) for k in (kinds[i] for i in rng.permutation(n_dep))]
     pools = _pools(rng, Z, int(rng.integers(1, 3)), limits=rng.integers(3) == 0)
-    spec = _world(rng, deploys, pools, cat, R, Z, pick(rng, [8, 16]), hpa_sync_s=pick(rng, [0, 60]))
-    sc = _scenarios(rng, R, (0, 60, 300, 480))
-    return spec, sc, _load(rng, spec.n_steps, [pick(rng, HIS) for _ in deploys])
+    spec = _world(rng, deploys, pools, cat, R, Z, slots or pick(rng, [8, 16]), hpa_sync_s=pick(rng, [0, 60]))
+    sc = _scenarios(rng, R, (0, 60, 300, 480), n=n)
+    return spec, sc, _load(rng, spec.n_steps, [pick(rng, HIS) for _ in deploys], n)
 
 
-def draw(profile: str, seed: int):
-    """(WorldSpec, ScenarioSet, load [T][D][130] int32) of a profile's world number `seed`."""
+# ---------------------------------------------------------------------------
+# wide profiles: catalogs beyond one wave, 3-8 regions, several workgroups,
+# shared traces, the slot / pool / weight / mask limits of the engines
+# ---------------------------------------------------------------------------
+N_WIDE = 600  # two full 256-thread workgroups and a ragged third
+D1_KS = (63, 64, 65, 127, 128, 129, 200)
+
+
+def _catalog_wide(rng, K, zero_cap=True):
+    """K types of few distinct shapes, so many share a pod capacity and the
+    runs of equal capacity are long (they straddle positions 63 / 64 and
+    127 / 128 of the capacity-sorted order); catalog order is random, so a
+    type's index says nothing about its capacity. Index 0 is the base group's
+    type; the last index is a type of the smallest shape (2 vCPU, 4 GiB, 8
+    pods), so (ties keep catalog order) it is last in the capacity order among
+    the types that hold a pod, at a price that wins small claims.
+    With zero_cap some types hold no pod at all (max_pods 0)."""
+    vcpu = np.array([2] + [pick(rng, [2, 2, 4, 4, 8, 16, 32]) for _ in range(K - 1)], np.int32)
+    mem = np.array([8.0] + [float(v * pick(rng, [2, 4, 8])) for v in vcpu[1:]], np.float64)
+    pods = np.array([29] + [pick(rng, [8, 17, 29, 58, 110]) for _ in range(K - 1)], np.int32)
+    if zero_cap:
+        none = 1 + rng.choice(K - 2, size=max(1, K // 25), replace=False)
+        pods[none] = 0
+    vcpu[K - 1], mem[K - 1], pods[K - 1] = 2, 4.0, 8
+    od = np.array([int(v * rng.integers(35000, 60001)) for v in vcpu], np.int64)
+    od[K - 1] = 2 * 20000  # and the cheapest for the small claims it holds
+    names = ["m6i.large"] + [f"t{k}.x" for k in range(1, K)]
+    return Catalog(names, vcpu, mem, pods, od)
+
+
+def _prices_wide(rng, cat, R, Z):
+    """Prices of a wide catalog: per-type discounts by region and zone with
+    20 % hour-by-hour noise, so among the many types of one shape the
+    cheapest changes with the hour, the region and the zone mask, and (price
+    following the vCPU count) with the size of the claim. Types that hold no
+    pod are the cheapest of all: a scan that admitted one would choose it."""
+    K = cat.k
+    od = cat.od_uph[None, :] * (1.0 + 0.08 * np.arange(R))[:, None]
+    odz = od[:, None, :, None] * (1.0 + 0.02 * rng.uniform(-1, 1, size=(R, 1, K, Z)))
+    disc = rng.uniform(0.3, 0.7, size=(R, 1, K, Z))
+    spot = odz * disc * (1.0 + 0.2 * rng.normal(size=(R, 24, K, Z)))
+    spot = np.clip(spot, 0.2 * odz, 0.95 * odz)
+    odh = odz * (1.0 + 0.05 * rng.uniform(-1, 1, size=(R, 24, K, Z)))
+    tile = np.zeros((R, 24, K, Z, 2), np.int32)
+    tile[..., 0] = np.rint(spot)
+    tile[..., 1] = np.rint(odh)
+    tile[:, :, cat.max_pods == 0] //= 8
+    miss = pick(rng, [0.0, 0.1, 0.3])
+    if miss > 0:
+        gone = rng.random(size=(R, 1, K, Z, 2)) < miss
+        if rng.integers(2):
+            gone = gone | (rng.random(size=tile.shape) < miss / 3)
+        gone[:, :, 0, 0, 1] = False
+        tile[np.broadcast_to(gone, tile.shape)] = 0
+    return tile
+
+
+def _regions(rng, layout, R, n=N_WIDE, B=256):
+    """The region column of n scenarios over workgroups of B.
+    sorted: ascending, equal shares (each block spans a few regions, every
+      block's lowest region differs);
+    shuffled: every block spans all R regions;
+    sorted_last: ascending over the full blocks (boundaries off the block
+      edges: the first block spans two regions or more), the ragged last block
+      holds the highest region alone (its lowest region + span runs past R);
+    aligned: one region per block (span 1), three distinct regions."""
+    i = np.arange(n)
+    if layout == "sorted":
+        reg = i * R // n
+    elif layout == "shuffled":
+        reg = rng.permutation(i % R)
+    elif layout == "sorted_last":
+        full = n // B * B
+        reg = np.where(i < full, np.minimum((i + B // 4) * (R - 1) // full, R - 2), R - 1)
+    else:
+        reg = np.sort(rng.choice(R, size=3, replace=False))[np.minimum(i // B, 2)]
+    return reg.astype(np.uint8)
+
+
+LAYOUTS = ("sorted", "shuffled", "sorted_last", "aligned")
+
+
+def layout_span(layout, R, n=N_WIDE, B=256):
+    """The largest number of regions one workgroup of B scenarios spans."""
+    reg = _regions(np.random.default_rng(0), layout, R, n, B).astype(int)
+    return max(int(reg[b:b + B].max() - reg[b:b + B].min()) + 1 for b in range(0, n, B))
+
+
+def _share_traces(rng, sc, load, seed):
+    """Every third world reads shared traces: n_traces in {7, 64, 130} (no
+    divisor of 600) with a first_id that is no multiple of it, and per-scenario
+    target and replica-bound overrides, so scenarios on one trace differ. One
+    world in four has first_id = 2^33 + a draw."""
+    n = sc.n
+    if (seed // 4) % 4 == 0:
+        sc.first_id += 1 << 33
+    if seed % 3 != 0:
+        return load
+    nt = (7, 64, 130)[(seed // 3) % 3]
+    if sc.first_id % nt == 0:
+        sc.first_id += 1 + int(rng.integers(nt - 1))
+    sc.n_traces = nt
+    sc.target_util_pct = rng.integers(30, 96, size=n).astype(np.int16)
+    sc.max_replicas = rng.integers(5, 61, size=n).astype(np.int16)
+    return np.ascontiguousarray(load[:, :, :nt])
+
+
+def _cap_masks(pools, Z, limit):
+    """At most `limit` distinct non-zero zone masks over every patch of the
+    pools (the single-deployment engine holds D1_MAX_ZI = 8): later ones are
+    folded onto the first `limit`."""
+    seen = []
+    for p in pools:
+        for x in [p.base] + [p.profile[s] for s in range(3)]:
+            m = x.zone_mask & ((1 << Z) - 1)
+            if m and m not in seen:
+                if len(seen) < limit:
+                    seen.append(m)
+                else:
+                    x.zone_mask = seen[m % limit]
+    return len(seen)
+
+
+def _d1_wide(rng, seed, n=N_SCEN, n_weights=None, n_masks=None):
+    """kind 0: 3-4 pools, <= 8 slots; kind 1: 9-16 slots, <= 2 pools; kind 2:
+    9-16 slots, 3-4 pools and exactly 8 distinct carbon weights. n_weights /
+    n_masks: the boundary worlds' exact counts of distinct carbon weights and
+    zone masks (4 pools over 4 zones)."""
+    kind = seed % 3
+    K = D1_KS[(seed // 3) % len(D1_KS)]
+    R = pick(rng, [1, 1, 2, 3, 5, 8])
+    Z = int(rng.integers(2, 5))
+    n_pools = int(rng.integers(3, 5)) if kind != 1 else int(rng.integers(1, 3))
+    slots = int(rng.integers(9, 17)) if kind != 0 else int(rng.integers(3, 9))
+    if n_masks:
+        Z, n_pools = 4, 4
+    elif K <= 65 and seed % 2 == 0:
+        # the kernel's four 16 KiB rings leave 15 KiB for prices, ci and J under its
+        # 80 KiB bound: at 63 types and more only one region of one zone fits (lds_tab 1)
+        R, Z = 1, 1
+    cat = _catalog_wide(rng, K, zero_cap=K != 65 and rng.integers(3) > 0)
+    hi = pick(rng, HIS)
+    rules = pick(rng, ["default", "ring"])
+    stab_set = (0, 60, 300, 450, 480) if rules == "ring" else (0, 60, 120, 300)
+    dep = _hpa(rng, rules=rules, stab_set=stab_set, tol_set=(0.1, 0.0, 0.25))
+    pools = _pools(rng, Z, n_pools)
+    if n_masks:
+        masks = [int(m) for m in 1 + rng.permutation(15)[:n_masks]]
+        patches = [x for p in pools for x in [p.base] + [p.profile[s] for s in range(3)]]
+        for j, x in enumerate(patches):
+            x.zone_mask = masks[j] if j < n_masks else pick(rng, [0] + masks)
+    else:
+        _cap_masks(pools, Z, 8)
+    spec = _world(rng, [dep], pools, cat, R, Z, slots, hpa_sync_s=pick(rng, [0, 60]))
+    spec.base_nodes = int(rng.integers(0, 2))
+    sc = _scenarios(rng, R, stab_set, n=n)
+    if R > 1:
+        sc.region = rng.integers(0, R, size=n).astype(np.uint8)
+    n_weights = n_weights or (8 if kind == 2 else None)
+    if n_weights:
+        ws = np.arange(n_weights) * 0.25 + rng.uniform(0.0, 0.2)
+        sc.carbon_weight = ws[rng.permutation(np.arange(n) % n_weights)]
+    return spec, sc, _load(rng, spec.n_steps, [hi], n)
+
+
+def _wide_geo(rng, seed, Ks, need_all_hours):
+    """(catalog, R, Z, layout) of a gk_wide / sk_wide world. The layout cycles
+    with the seed; where all 24 hourly tiles must fit in LDS beside the
+    catalog (plan_launch: span x Z <= 4 up to 65 types, <= 2 at 130, never at
+    200) the catalog, the zones and R are drawn inside that bound (a span of
+    R >= 3 then has one zone), otherwise outside it."""
+    layout = LAYOUTS[seed % 4]
+    R = int(rng.integers(3, 9))
+    if need_all_hours:
+        small = [k for k in Ks if k <= 65]
+        if layout == "aligned":        # span 1
+            K = pick(rng, [k for k in Ks if k <= 130])
+            Z = 2 if K > 65 else int(rng.integers(2, 5))
+        elif layout == "shuffled":     # span R
+            K, Z, R = pick(rng, small), 1, int(rng.integers(3, 5))
+        elif layout == "sorted":       # span 2 of R = 3
+            K, Z, R = pick(rng, small), 2, 3
+        else:                          # sorted_last: span 2 of R = 3 (one region per full block, +1)
+            K, Z, R = pick(rng, small), 2, 3
+    else:
+        K = pick(rng, [k for k in Ks if k > 65])
+        Z = int(rng.integers(3, 5)) if K <= 130 else int(rng.integers(2, 5))
+        if layout == "aligned":        # span 1 stages all hours up to 130 types
+            K = max(Ks)
+    return _catalog_wide(rng, K, zero_cap=K != 65), R, Z, layout
+
+
+def _finish_wide(rng, seed, world, R, layout):
+    spec, sc, load = world
+    spec.base_nodes = int(rng.integers(0, 2))
+    sc.region = _regions(rng, layout, R)
+    return spec, sc, _share_traces(rng, sc, load, seed)
+
+
+def _gk_wide(rng, seed):
+    """seed % 4: the region layout; (seed // 4) % 2: all 24 hourly tiles
+    staged or one hour at a time; seed % 3 == 0: shared traces; every other
+    world has one deployment (as gk_single), the rest several (as gk_multi)."""
+    cat, R, Z, layout = _wide_geo(rng, seed, (65, 130, 200), need_all_hours=(seed // 4) % 2 == 0)
+    # (one zone leaves drift inert, and with it one of gk_single's reasons: several deployments there)
+    draw1 = _gk_single if (seed // 2) % 2 == 0 and Z > 1 else _gk_multi
+    return _finish_wide(rng, seed, draw1(rng, geo=(cat, R, Z), n=N_WIDE), R, layout)
+
+
+def _sk_wide(rng, seed):
+    """seed % 4: the region layout; (seed // 4) % 2: 8 or 16 node slots; K = 64
+    where (seed // 8) % 4 == 0, so 64 types meet both slot counts; seed % 3 == 0:
+    shared traces. Every world stages all 24 hours (sk_eligible)."""
+    Ks = (64,) if (seed // 8) % 4 == 0 else (65, 130)
+    cat, R, Z, layout = _wide_geo(rng, seed, Ks, need_all_hours=True)
+    return _finish_wide(rng, seed, _sk(rng, geo=(cat, R, Z), n=N_WIDE, slots=(8, 16)[(seed // 4) % 2]), R, layout)
+
+
+def draw(profile: str, seed: int, n: int = N_SCEN):
+    """(WorldSpec, ScenarioSet, load [T][D][n] int32) of a profile's world
+    number `seed`. n: the scenario count of the `loop` profile's worlds (130;
+    600 for several workgroups); the wide profiles fix their own."""
     rng = np.random.default_rng([20251205, _PIDX[profile], seed])
+    if profile == "d1_wide":
+        return _d1_wide(rng, seed)
+    if profile == "gk_wide":
+        return _gk_wide(rng, seed)
+    if profile == "sk_wide":
+        return _sk_wide(rng, seed)
     if profile.startswith("d1_"):
         return _d1(rng, profile)
     if profile == "gk_single":
@@ -370,8 +623,18 @@ def draw(profile: str, seed: int):
     if profile == "sk":
         return _sk(rng)
     if profile == "loop":
-        return _d1(rng, "d1_default" if seed % 2 == 0 else "loop_drift")
+        return _d1(rng, "d1_default" if seed % 2 == 0 else "loop_drift", n)
     raise KeyError(profile)
+
+
+def limit_world(which: str):
+    """The d1_wide worlds at the single-deployment engine's limits: 8 distinct
+    carbon weights or zone masks stay on it (engine 2), 9 go to the general
+    kernel (D1_MAX_WC, D1_MAX_ZI)."""
+    what, count = {"weights8": ("w", 8), "weights9": ("w", 9), "masks8": ("m", 8), "masks9": ("m", 9)}[which]
+    seed = 4 if what == "w" else 5  # kinds 1 (two pools) and 2 (four pools)
+    rng = np.random.default_rng([20251205, 98, seed])
+    return _d1_wide(rng, seed, n_weights=count if what == "w" else None, n_masks=count if what == "m" else None)
 
 
 def boundary_world(which: str):

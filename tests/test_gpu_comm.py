@@ -104,3 +104,46 @@ def test_cross_rank_merge_keeps_all_when_nothing_dominates(eng):
     assert len(got) == nranks * cap
     with pytest.raises(abi.CckaError):
         eng.debug_pareto_merge(g, [cap] * nranks, capacity=cap)
+
+
+def _diagonal_grids(rng, n, noise):
+    """n candidates along an anti-diagonal of (cost, SLO): with noise 0 none
+    dominates another; with noise neighbours do, all along the diagonal."""
+    a = _random_grids(rng, 0, n)
+    k = np.arange(n)
+    a["cost_uphmin"] = 4 * k + (rng.integers(0, noise, n) if noise else 0)
+    a["slo_minutes"] = 4 * (n - k) + (rng.integers(0, noise, n) if noise else 0)
+    a["gco2"] = rng.integers(0, 3, n).astype(np.float64) * 0.5 if noise else 1.0
+    return a
+
+
+# pareto_compact_kernel writes the survivors in chunks of 1024 candidates with
+# a running base: one chunk exactly, one entry into the second, and three chunks
+@pytest.mark.parametrize("case", ["all_2500", "random_2500", "n1024", "n1025", "duplicates"])
+def test_merge_compaction_beyond_one_chunk(eng, case):
+    rng = np.random.default_rng(len(case))
+    if case == "all_2500":
+        allg = _diagonal_grids(rng, 2500, 0)
+    elif case == "random_2500":
+        allg = _diagonal_grids(rng, 2500, 12)
+    elif case == "duplicates":  # equal rows: neither dominates the other, both stay
+        allg = _diagonal_grids(rng, 1300, 12)
+        allg[1::2] = allg[0::2]
+        allg["grid"] = np.arange(len(allg))
+    else:
+        allg = _diagonal_grids(rng, int(case[1:]), 12)
+    n = len(allg)
+    keep = po.pareto({k: allg[k] for k in allg.dtype.names})
+    want = allg[keep]
+    if case == "all_2500":
+        assert len(want) == n
+    else:  # survivors and casualties in every chunk of 1024 candidates
+        for c0 in range(0, n, 1024):
+            inside = int(((keep >= c0) & (keep < c0 + 1024)).sum())
+            assert 0 < inside and (inside < min(1024, n - c0) or n - c0 == 1), (case, c0, inside)
+    if case == "duplicates":
+        assert np.all(np.isin(keep[keep % 2 == 0] + 1, keep))
+    nranks = 2 if n % 2 == 0 else 1
+    got = eng.debug_pareto_merge(allg.reshape(nranks, n // nranks), [n // nranks] * nranks)
+    assert np.array_equal(got, want), (case, len(got), len(want))
+    assert np.all(np.diff(got["grid"]) > 0)

@@ -19,6 +19,12 @@ another engine than its profile intends is a failure, not a skip.
              against the oracle's replay of its recorded actions, features
              included; on seeds 0-49 the launched loop (engine 3) equals it
 
+  d1_wide    as d1_*; gk_wide as gk_*; sk_wide as sk: the wide profiles (100
+             worlds each, 10 per case): catalogs of 63-200 types, 3-8 regions,
+             600 scenarios, shared traces. The launch plan of every run
+             (ccka_debug_last_plan) is asserted against the engine that ran
+             and tallied; test_wide_paths_all_ran holds the path counts.
+
 A failure names (profile, seed, engine mode): random_worlds.draw(profile,
 seed) reproduces the world. Seeds that once failed are frozen below as named
 regression cases."""
@@ -42,7 +48,54 @@ D1_MODES = [(0, "auto", 2), (1, "general", 1)]
 GK_MODES = [(0, "auto", 1)]
 SK_MODES = [(0, "auto", 5), (3, "cooperative", 5), (2, "lockstep", 1)]
 MODES = {"d1_default": D1_MODES, "d1_rules": D1_MODES, "d1_sync15": D1_MODES, "d1_keda": D1_MODES,
-         "d1_disrupt": D1_MODES, "gk_single": GK_MODES, "gk_multi": GK_MODES, "sk": SK_MODES}
+         "d1_disrupt": D1_MODES, "gk_single": GK_MODES, "gk_multi": GK_MODES, "sk": SK_MODES,
+         "d1_wide": D1_MODES, "gk_wide": GK_MODES, "sk_wide": SK_MODES}
+WIDE_PER_CHUNK = 10
+D1_FIELDS = ("lds_tab", "nw", "nzi", "jt", "inst")
+GK_FIELDS = ("span", "all_hours", "hlen", "lclaims")
+# (profile, seed) -> the launch plan of its automatic run, and the world's R
+PLANS = {}
+
+
+def lane_local_fits(plan, spec):
+    """abi_rollout.cpp's size rule for the skewed schedule's lane-local
+    provisioning: the per-lane NodeClaim columns (nmax x (7 + dmax) ints for
+    each of 256 lanes; kparams.h kernel_dims) beside the rest of the
+    workgroup's LDS within 160 KiB, for catalogs of at most 64 types."""
+    dmax = 2 if len(spec.deploys) <= 2 else 4
+    nmax = 8 if spec.max_nodes <= 8 else 16
+    need = nmax * (7 + dmax) * 256 * 4
+    rest = plan["lds"] - need if plan["lclaims"] == 1 else plan["lds"]
+    return spec.catalog.k <= 64 and (rest + 15) // 16 * 16 + need <= 160 * 1024
+
+
+def check_plan(plan, engine_ran, spec, sc, what, lpw=0, cus=0):
+    """The plan belongs to the engine that ran: no single-deployment field on
+    the general kernel and the reverse; the workgroup count, the shared-trace
+    flag, and on the single-deployment engine the table sizes and the
+    instantiation, as the world and the scenario set imply."""
+    assert plan["trace_mod"] == (1 if sc.n_traces else 0), f"{what}: plan {plan}"
+    assert plan["lds"] > 0, f"{what}: plan {plan}"
+    if engine_ran == 2:
+        assert all(plan[f] == -1 for f in GK_FIELDS), f"{what}: general-kernel field in plan {plan}"
+        assert plan["inst"] == (16 if spec.max_nodes > 8 else 8) * 100 + (4 if len(spec.pools) > 2 else 2), f"{what}: {plan}"
+        # scenarios per wave: the forced value, or abi_rollout.cpp d1_lpw's 32..64 by batch size
+        per_wave = lpw or min(64, max(32, -(-sc.n // (8 * cus))))
+        assert plan["grid"] == -(-(-(-sc.n // per_wave)) // 4), f"{what}: plan {plan}"
+        zall = (1 << spec.n_zones) - 1
+        masks = {x.zone_mask & zall for p in spec.pools for x in [p.base] + [p.profile[q] for q in range(3)]} - {0}
+        weights = 1 if sc.carbon_weight is None else len(np.unique(sc.carbon_weight))
+        assert plan["nzi"] == max(1, len(masks)) and plan["nw"] == weights, f"{what}: plan {plan}"
+        assert plan["jt"] == int(rw.pod_cap1(spec).max()) + 1, f"{what}: plan {plan}"
+        assert plan["lds_tab"] in (0, 1), f"{what}: plan {plan}"
+    else:
+        assert all(plan[f] == -1 for f in D1_FIELDS), f"{what}: single-deployment field in plan {plan}"
+        assert plan["grid"] == (sc.n + 255) // 256, f"{what}: plan {plan}"
+        assert 1 <= plan["span"] <= spec.n_regions and plan["all_hours"] in (0, 1) and plan["hlen"] >= 0, f"{what}: {plan}"
+        # lane-local provisioning: only on the skewed schedule, only where the size
+        # rule admits it (a build without the branch takes it nowhere)
+        fits = engine_ran == 5 and lane_local_fits(plan, spec)
+        assert plan["lclaims"] in (0, int(fits)), f"{what}: lane-local fits {fits}, plan {plan}"
 
 
 def _lpw(engine, v):
@@ -79,15 +132,22 @@ def check_world(engine, profile, seed, world=None, modes=None):
             _lpw(engine, lpw)
             rg, tg = run_engine(engine, spec, sc, load=load, traj=True)
             got = engine.last_engine()[0]
+            plan = engine.last_plan()
         finally:
             engine.set_engine(0)
             _lpw(engine, 0)
         assert got == want, f"{what}: ran on engine {got}, expected {want}"
+        check_plan(plan, got, spec, sc, what, lpw, engine.device_info()[1])
+        if label == "cooperative":
+            assert plan["lclaims"] == 0, f"{what}: plan {plan}"
+        if mode == 0 and profile in rw.WIDE_PROFILES:
+            PLANS[profile, seed] = dict(plan, R=spec.n_regions, K=spec.catalog.k, slots=spec.max_nodes,
+                                        fits=got == 5 and lane_local_fits(plan, spec))
         _named(what, lambda: compare(rg, rc, tg, tc))
 
 
-def check_loop(engine, seed, launched):
-    spec, sc, load = rw.draw("loop", seed)
+def check_loop(engine, seed, launched, n=rw.N_SCEN):
+    spec, sc, load = rw.draw("loop", seed, n)
     ws, bs = configs.mlp_weights(seed)
     engine.set_world(spec)
     engine.set_scenarios(sc)
@@ -121,10 +181,84 @@ def check_loop(engine, seed, launched):
 
 
 @pytest.mark.parametrize("chunk", range(CHUNKS))
-@pytest.mark.parametrize("profile", list(MODES))
+@pytest.mark.parametrize("profile", [p for p in MODES if p in rw.PROFILES])
 def test_random_worlds_match_oracle(engine, profile, chunk):
     for seed in range(chunk * PER_CHUNK, (chunk + 1) * PER_CHUNK):
         check_world(engine, profile, seed)
+
+
+@pytest.mark.parametrize("chunk", range(rw.WIDE_SEEDS // WIDE_PER_CHUNK))
+@pytest.mark.parametrize("profile", list(rw.WIDE_PROFILES))
+def test_wide_worlds_match_oracle(engine, profile, chunk):
+    for seed in range(chunk * WIDE_PER_CHUNK, (chunk + 1) * WIDE_PER_CHUNK):
+        check_world(engine, profile, seed)
+
+
+def test_wide_paths_all_ran(engine):
+    """Every path the wide profiles are drawn for ran in at least 10 of a
+    profile's 100 worlds (their automatic runs, tallied by the cases above; a
+    world this process has not run yet is run here). The sub-kinds are chosen
+    by the seed, so the counts are fixed by the generator.
+
+    The skewed schedule's lane-local provisioning is compiled into variant
+    builds only (rollout_sk.hip, CCKA_SK_LF2; the main build's kernels hold the
+    cooperative scans alone). Every run asserts that a world takes it only
+    where abi_rollout.cpp's rule admits it (check_plan); here at least 10
+    worlds of 8 slots must be admitted, at least 10 of 16 slots and <= 64
+    types refused by size, and the library takes the path in all the admitted
+    worlds or in none: under CCKA_TEST_LIB=<a -DCCKA_SK_LF2=1 variant> both
+    paths are thereby asserted at >= 10 worlds (DESIGN.md records that run)."""
+    for profile in rw.WIDE_PROFILES:
+        for seed in range(rw.WIDE_SEEDS):
+            if (profile, seed) not in PLANS:
+                check_world(engine, profile, seed, modes=MODES[profile][:1])
+    def count(profile, pred):
+        return sum(1 for (p, _), v in PLANS.items() if p == profile and pred(v))
+    want = {}
+    for profile in ("gk_wide", "sk_wide"):
+        want[profile, "span 1"] = count(profile, lambda v: v["span"] == 1)
+        want[profile, "span R"] = count(profile, lambda v: v["span"] == v["R"] and v["R"] >= 3)
+        want[profile, "span between"] = count(profile, lambda v: 1 < v["span"] < v["R"])
+        want[profile, "shared traces"] = count(profile, lambda v: v["trace_mod"] == 1)
+        want[profile, "own traces"] = count(profile, lambda v: v["trace_mod"] == 0)
+        want[profile, "several workgroups"] = count(profile, lambda v: v["grid"] > 1)
+    want["gk_wide", "all_hours 0"] = count("gk_wide", lambda v: v["all_hours"] == 0)
+    want["gk_wide", "all_hours 1"] = count("gk_wide", lambda v: v["all_hours"] == 1)
+    assert count("sk_wide", lambda v: v["all_hours"] != 1) == 0
+    for on in (0, 1):
+        want["d1_wide", f"lds_tab {on}"] = count("d1_wide", lambda v: v["lds_tab"] == on)
+    for inst in (804, 1602, 1604):
+        want["d1_wide", f"instantiation {inst}"] = count("d1_wide", lambda v: v["inst"] == inst)
+    want["d1_wide", "8 carbon weights"] = count("d1_wide", lambda v: v["nw"] == 8)
+    want["sk_wide", "cooperative provisioning"] = count("sk_wide", lambda v: v["lclaims"] == 0)
+    want["sk_wide", "lane-local admitted, 8 slots"] = count("sk_wide", lambda v: v["fits"] and v["slots"] <= 8)
+    want["sk_wide", "lane-local refused by size, 16 slots"] = count(
+        "sk_wide", lambda v: not v["fits"] and v["slots"] > 8 and v["K"] <= 64)
+    want["sk_wide", "lane-local refused by catalog"] = count("sk_wide", lambda v: v["K"] > 64)
+    lane_local, fits = count("sk_wide", lambda v: v["lclaims"] == 1), count("sk_wide", lambda v: v["fits"])
+    assert lane_local in (0, fits), f"lane-local provisioning in {lane_local} of the {fits} worlds the rule admits"
+    if lane_local:  # == fits: the counts above hold for the path itself
+        want["sk_wide", "lane-local provisioning"] = lane_local
+    print(want)
+    short = {k: v for k, v in want.items() if v < 10}
+    assert not short, f"paths that ran in fewer than 10 worlds: {short}"
+
+
+@pytest.mark.parametrize("which", ["weights8", "weights9", "masks8", "masks9"])
+def test_d1_limit_worlds(engine, which):
+    """8 distinct carbon weights / zone masks stay on the single-deployment
+    engine, 9 go to the general kernel (D1_MAX_WC / D1_MAX_ZI); all four equal
+    the oracle."""
+    want = 1 if which.endswith("9") else 2
+    check_world(engine, "limit_" + which, 0, world=rw.limit_world(which),
+                modes=[(0, "auto", want), (1, "general", 1)])
+
+
+@pytest.mark.parametrize("chunk", range(2))
+def test_closed_loops_over_several_workgroups(engine, chunk):
+    """The loop profile's first 20 worlds at 600 scenarios: the fused kernel on three workgroups."""
+    for seed in range(chunk * 10, (chunk + 1) * 10):
+        check_loop(engine, seed, launched=False, n=rw.N_WIDE)
 
 
 @pytest.mark.parametrize("chunk", range(CHUNKS))
