@@ -31,7 +31,7 @@ SELECT_MAX, SELECT_MIN, SELECT_DISABLED = 0, 1, 2
 HPA_PODS, HPA_PERCENT = 1, 2
 
 STATUS = {0: "OK", -1: "EINVAL", -2: "ENOMEM", -3: "EHIP", -4: "ERCCL",
-          -5: "EPARITY", -6: "ESTATE", -7: "ENODEV"}
+          -5: "EPARITY", -6: "ESTATE", -7: "ENODEV", -8: "EOVERFLOW"}
 
 
 class ItType(C.Structure):

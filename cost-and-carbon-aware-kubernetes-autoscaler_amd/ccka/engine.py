@@ -231,6 +231,45 @@ class Engine:
                   "ccka_debug_grid_stat")
         return _grid_array(out, ng)
 
+    TOTALS_COLUMNS = (("cost_uphmin", np.int64), ("slo_minutes", np.int32), ("pending_pod_minutes", np.int64),
+                      ("node_min_spot", np.int32), ("node_min_od", np.int32), ("launches", np.int32),
+                      ("deletions", np.int32), ("energy_wmin", np.float64), ("gco2", np.float64))
+
+    def debug_totals(self, cols: dict) -> abi.Totals:
+        """Internal: ccka_get_totals' reduction on given result columns (a
+        mapping with TOTALS_COLUMNS); raises CckaError on CCKA_EOVERFLOW."""
+        a = [np.ascontiguousarray(cols[k], dt) for k, dt in self.TOTALS_COLUMNS]
+        n = len(a[0])
+        assert all(x.shape == (n,) for x in a)
+        fn = self.lib.ccka_debug_totals
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 9 + [C.c_int64, C.POINTER(abi.Totals)]
+        t = abi.Totals()
+        self._chk(fn(self.ctx, *[x.ctypes.data for x in a], n, C.byref(t)), "ccka_debug_totals")
+        return t
+
+    def debug_traj_stage(self, records: int = 0):
+        """Internal: staging capacity in records of trajectory()'s device
+        transpose (0 = the default 4 Mi)."""
+        fn = self.lib.ccka_debug_traj_stage
+        fn.argtypes = [C.c_void_p, C.c_int64]
+        self._chk(fn(self.ctx, records), "ccka_debug_traj_stage")
+
+    def debug_trace_layout(self, trace: np.ndarray, dp: int = 0, lpw: int = 0, sentinel: int = 0x5EA7BEEF) -> np.ndarray:
+        """Internal: the skewed schedule's [NL][T][DP] copy (dp > 0) or the
+        single-deployment kernel's wave-tiled copy (dp == 0, lanes per wave
+        lpw, D == 1) of a [T][D][NL] int32 trace: the whole output buffer,
+        flat, filled with `sentinel` before the kernel ran."""
+        a = np.ascontiguousarray(trace, np.int32)
+        T, D, NL = a.shape
+        cnt = NL * T * dp if dp else T * ((NL + lpw - 1) // max(1, lpw) * lpw)
+        out = np.zeros(cnt, np.int32)
+        fn = self.lib.ccka_debug_trace_layout
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                       C.c_void_p, C.c_int64]
+        self._chk(fn(self.ctx, a.ctypes.data, T, D, NL, dp, lpw, sentinel, out.ctypes.data, cnt),
+                  "ccka_debug_trace_layout")
+        return out
+
     # ---- multi-GPU (RCCL over xGMI) ----
     def comm_init(self, uid: bytes | None = None, nranks: int = 1, rank: int = 0):
         """RCCL communicator of this context; uid = None creates a fresh id

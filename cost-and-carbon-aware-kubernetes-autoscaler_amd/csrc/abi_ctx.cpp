@@ -12,6 +12,7 @@
 #include <new>
 
 #include "ctx.h"
+#include "host_rules.h"
 
 using namespace ccka;
 
@@ -515,18 +516,17 @@ int ccka_set_world(ccka_ctx* c, const ccka_world* w) {
   return CCKA_OK;
 }
 
-static int alloc_results(ccka_ctx* c) {
-  free_results(c);
-  const int64_t N = c->N;
+}  // extern "C"
+
+// the result columns of N scenarios carved out of one allocation at p (the
+// SoA the kernels write): returns its size in bytes; p == nullptr: the size alone
+int64_t carve_results(char* p, int64_t N, ResultPtrs* out) {
   // 8-byte fields first, then 4-byte fields; each array 256-B aligned
   auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
   const int64_t b8 = up(N * 8), b4 = up(N * 4);
   const int64_t total = 4 * b8 + 10 * b4;
-  if (!all_or_none(c->d_res.resize(total) && c->d_parts.resize(1024 * 11 + 1) && c->d_totals.reserve(1), c->d_res,
-                   c->d_parts))
-    return fail(c, CCKA_ENOMEM, "results alloc (%lld scenarios)", (long long)N);
-  char* p = c->d_res;
-  ResultPtrs& k = c->res;
+  if (!p) return total;
+  ResultPtrs& k = *out;
   k.cost = (int64_t*)p; p += b8;
   k.energy = (double*)p; p += b8;
   k.gco2 = (double*)p; p += b8;
@@ -541,6 +541,19 @@ static int alloc_results(ccka_ctx* c) {
   k.final_nodes = (int32_t*)p; p += b4;
   k.last_choice = (uint32_t*)p; p += b4;
   k.hash = (uint32_t*)p;
+  return total;
+}
+
+extern "C" {
+
+static int alloc_results(ccka_ctx* c) {
+  free_results(c);
+  const int64_t N = c->N;
+  if (!all_or_none(c->d_res.resize(carve_results(nullptr, N, nullptr)) &&
+                       c->d_parts.resize(kTotalsParts * 11 + 1) && c->d_totals.reserve(1),
+                   c->d_res, c->d_parts))
+    return fail(c, CCKA_ENOMEM, "results alloc (%lld scenarios)", (long long)N);
+  carve_results(c->d_res, N, &c->res);
   return CCKA_OK;
 }
 
@@ -648,8 +661,7 @@ int ccka_set_load(ccka_ctx* c, const int32_t* load, int64_t count) {
 int ccka_gen_load(ccka_ctx* c, const ccka_trace_gen* g) {
   if (!c || !g) return CCKA_EINVAL;
   if (!c->have_sc) return fail(c, CCKA_ESTATE, "set_scenarios first");
-  if (g->base_hi < g->base_lo || g->amp_hi_pm < g->amp_lo_pm || g->burst_len < 0)
-    return fail(c, CCKA_EINVAL, "trace generator ranges invalid");
+  if (const char* why = trace_gen_invalid(*g)) return fail(c, CCKA_EINVAL, "trace generator invalid: %s", why);
   (void)hipSetDevice(c->device);
   int rc;
   if ((rc = ensure_load(c)) != CCKA_OK) return rc;

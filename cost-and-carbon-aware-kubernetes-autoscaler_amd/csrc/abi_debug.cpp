@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "host_rules.h"
 
 using namespace ccka;
 
@@ -169,6 +170,65 @@ int ccka_debug_mlp_stamps(ccka_ctx* c, int32_t enable) {
 int ccka_debug_stamps(ccka_ctx* c, unsigned long long* out8) {
   if (!c || !out8 || !c->d_stamps) return CCKA_EINVAL;
   HIPCHK(c, hipMemcpy(out8, c->d_stamps, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return CCKA_OK;
+}
+
+// Internal: ccka_get_totals' reduction (totals_of: the same partials rule,
+// buffers and overflow read-back) on caller-supplied result columns of n
+// scenarios instead of the last rollout's, so a test can feed sums no rollout
+// reaches. The columns are carved like a rollout's (carve_results). Needs no
+// world or scenarios; the totals, or CCKA_EOVERFLOW.
+int ccka_debug_totals(ccka_ctx* c, const int64_t* cost, const int32_t* slo, const int64_t* pend_min,
+                      const int32_t* nmin_spot, const int32_t* nmin_od, const int32_t* launches,
+                      const int32_t* deletions, const double* energy, const double* gco2, int64_t n,
+                      ccka_totals* out) {
+  if (!c || !cost || !slo || !pend_min || !nmin_spot || !nmin_od || !launches || !deletions || !energy || !gco2 ||
+      !out || n < 1 || n > (int64_t)1 << 31)
+    return CCKA_EINVAL;
+  (void)hipSetDevice(c->device);
+  DevBuf<char> d_res;
+  if (!d_res.resize(carve_results(nullptr, n, nullptr))) return fail(c, CCKA_ENOMEM, "totals columns (%lld)", (long long)n);
+  ResultPtrs r{};
+  carve_results(d_res, n, &r);
+  struct { void* dst; const void* src; size_t sz; } m[] = {
+      {r.cost, cost, 8}, {r.slo, slo, 4}, {r.pend_min, pend_min, 8}, {r.nmin_spot, nmin_spot, 4},
+      {r.nmin_od, nmin_od, 4}, {r.launches, launches, 4}, {r.deletions, deletions, 4}, {r.energy, energy, 8},
+      {r.gco2, gco2, 8}};
+  for (auto& x : m) HIPCHK(c, hipMemcpyAsync(x.dst, x.src, (size_t)n * x.sz, hipMemcpyHostToDevice, c->stream));
+  const int rc = totals_of(c, r, n, out);
+  (void)hipStreamSynchronize(c->stream);  // before the columns are freed
+  return rc;
+}
+
+// Internal: staging capacity in records of ccka_get_trajectory's transpose
+// (0 = the default 4 Mi), to run blocks of 1 < tc < T steps at test sizes.
+int ccka_debug_traj_stage(ccka_ctx* c, int64_t records) {
+  if (!c || records < 0) return CCKA_EINVAL;
+  c->traj_stage = records;
+  return CCKA_OK;
+}
+
+// Internal: one of the two trace copies on a caller-supplied [T][D][NL] trace,
+// the whole output buffer returned, padding included: DP > 0 runs
+// launch_trace_nt (sk_trace's copy, [NL][T][DP], trace_nt_count elements),
+// DP == 0 launch_trace_tile (d1_trace_tile's, D == 1, [wave][T][lpw],
+// trace_tile_count elements). The buffer is filled with `sentinel` first.
+int ccka_debug_trace_layout(ccka_ctx* c, const int32_t* in, int64_t T, int32_t D, int64_t NL, int32_t DP,
+                            int32_t lpw, int32_t sentinel, int32_t* out, int64_t out_count) {
+  if (!c || !in || !out || T < 1 || D < 1 || NL < 1 || T > 65535 || NL > (int64_t)1 << 31) return CCKA_EINVAL;
+  if (DP == 0 && (D != 1 || lpw < 1 || lpw > 64)) return CCKA_EINVAL;
+  if (DP != 0 && (D > DP || (DP != 2 && DP != 4 && DP != 8 && DP != 16))) return CCKA_EINVAL;
+  const int64_t cnt = DP ? trace_nt_count(NL, T, DP) : trace_tile_count(NL, T, lpw);
+  if (out_count != cnt) return fail(c, CCKA_EINVAL, "layout holds %lld ints, not %lld", (long long)cnt, (long long)out_count);
+  (void)hipSetDevice(c->device);
+  DevBuf<int32_t> d_in, d_out;
+  int rc;
+  if ((rc = dupload(c, d_in, in, (size_t)(T * D * NL))) != CCKA_OK) return rc;
+  if (!d_out.resize(cnt)) return fail(c, CCKA_ENOMEM, "layout buffer");
+  HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)d_out.get(), sentinel, (size_t)cnt, c->stream));
+  HIPCHK(c, DP ? launch_trace_nt(d_in, d_out, NL, T, D, DP, c->stream) : launch_trace_tile(d_in, d_out, NL, T, lpw, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)cnt * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // before the buffers are freed
   return CCKA_OK;
 }
 

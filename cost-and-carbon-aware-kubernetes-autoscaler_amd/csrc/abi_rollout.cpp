@@ -8,11 +8,9 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "host_rules.h"
 
 using namespace ccka;
-
-// staging records of ccka_get_trajectory's [N][T] -> [T][N] transpose (64 MiB)
-constexpr int64_t kTrajStageRecs = int64_t(4) << 20;
 
 // scenarios per wave of the single-deployment kernel: a wave's cost is the
 // union of its lanes' event paths, so when the batch is smaller than one full
@@ -36,7 +34,7 @@ static int d1_trace_tile(ccka_ctx* c) {
   if (!c->d1_world || c->hw.n_deploy != 1 || c->n_traces > 0 || !c->have_load) return CCKA_OK;
   const int32_t lpw = d1_lpw(c);
   if (c->load_w_lpw == lpw && c->d_load_w) return CCKA_OK;
-  const int64_t cnt = (int64_t)c->hw.n_steps * ((c->N + lpw - 1) / lpw * lpw);  // rows lpw wide
+  const int64_t cnt = trace_tile_count(c->N, c->hw.n_steps, lpw);  // rows lpw wide
   c->load_w_lpw = 0;
   if (!c->d_load_w.resize(cnt)) return CCKA_OK;
   HIPCHK(c, launch_trace_tile(c->d_load, c->d_load_w, c->N, c->hw.n_steps, lpw, c->stream));
@@ -51,7 +49,7 @@ static int sk_trace(ccka_ctx* c) {
   int dmax, nmax;
   kernel_dims(c->hw.n_deploy, c->hw.max_nodes, &dmax, &nmax);
   if (c->load_nt_dp == dmax && c->d_load_nt) return CCKA_OK;
-  const int64_t NL = load_cols(c), cnt = NL * c->hw.n_steps * dmax;
+  const int64_t NL = load_cols(c), cnt = trace_nt_count(NL, c->hw.n_steps, dmax);
   c->load_nt_dp = 0;
   if (!c->d_load_nt.resize(cnt)) return CCKA_OK;
   HIPCHK(c, launch_trace_nt(c->d_load, c->d_load_nt, NL, c->hw.n_steps, c->hw.n_deploy, dmax, c->stream));
@@ -390,11 +388,14 @@ int ccka_get_trajectory(ccka_ctx* c, ccka_traj_rec* out, int64_t count) {
   }
   // the single-deployment engine keeps [N][T] on the device: transpose tc
   // steps at a time into a bounded staging buffer (>= one step of N records,
-  // else kTrajStageRecs) and copy each block of steps to its place in out
+  // else kTrajStageRecs) and copy each block of steps to its place in out.
+  // tc comes from the capacity in force, not from the buffer's count(): the
+  // buffer only grows (reserve), so a larger one left by an earlier read-back
+  // would otherwise change the block size from call to call
   const int64_t N = c->N, T = count / N;
-  const int64_t cap = std::max<int64_t>(N, std::min<int64_t>(count, kTrajStageRecs));
+  const int64_t cap = traj_stage_cap(N, count, c->traj_stage);
   if (!c->d_traj_t.reserve(cap)) return fail(c, CCKA_ENOMEM, "trajectory staging alloc (%lld records)", (long long)cap);
-  const int64_t tc = std::max<int64_t>(1, c->d_traj_t.count() / N);
+  const int64_t tc = cap / N;
   for (int64_t t0 = 0; t0 < T; t0 += tc) {
     const int64_t n = std::min(tc, T - t0);
     HIPCHK(c, launch_traj_transpose(c->d_traj, c->d_traj_t, N, T, t0, n, c->stream));
@@ -428,13 +429,24 @@ int ccka_get_totals(ccka_ctx* c, ccka_totals* out) {
   if (!c || !out) return CCKA_EINVAL;
   if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
   (void)hipSetDevice(c->device);
+  return totals_of(c, c->res, c->N, out);
+}
+
+}  // extern "C"
+
+// the totals of N scenarios' result columns on the device (ccka_get_totals on
+// the last rollout's, ccka_debug_totals on uploaded ones): up to 1024 block
+// partials of >= 256 scenarios, the ordered final pass, the overflow word
+int totals_of(ccka_ctx* c, const ResultPtrs& res, int64_t N, ccka_totals* out) {
+  if (!all_or_none(c->d_parts.reserve(kTotalsParts * 11 + 1) && c->d_totals.reserve(1), c->d_parts, c->d_totals))
+    return fail(c, CCKA_ENOMEM, "totals buffers");
   TotParams q{};
-  q.res = c->res;
+  q.res = res;
   q.parts = (Part*)c->d_parts.get();
-  q.ovf = c->d_parts + 1024 * 11;
+  q.ovf = c->d_parts + kTotalsParts * 11;
   q.out = c->d_totals;
-  q.N = c->N;
-  const int nparts = (int)std::min<int64_t>(1024, (c->N + 255) / 256);
+  q.N = N;
+  const int nparts = (int)std::min<int64_t>(kTotalsParts, (N + 255) / 256);
   long long ovf = 0;
   HIPCHK(c, launch_totals(q, nparts, c->stream));
   HIPCHK(c, hipMemcpyAsync(out, c->d_totals, sizeof(ccka_totals), hipMemcpyDeviceToHost, c->stream));
@@ -443,6 +455,8 @@ int ccka_get_totals(ccka_ctx* c, ccka_totals* out) {
   if (ovf) return fail(c, CCKA_EOVERFLOW, "a fixed-point total exceeds int64 (ccka.h: ccka_totals)");
   return CCKA_OK;
 }
+
+extern "C" {
 
 // ---- the totals exchange, host halves (ccka.h: ccka_totals_pack / _finish) ----
 int ccka_totals_pack(const ccka_totals* in, int32_t nranks, int64_t* block, int32_t n) {

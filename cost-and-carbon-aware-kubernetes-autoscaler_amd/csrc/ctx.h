@@ -68,6 +68,7 @@ struct ccka_ctx {
   bool traj_valid = false;
   bool traj_nt = false;          // device records are [N][T] (single-deployment engine)
   Buf<ccka_traj_rec> d_traj_t;  // [T][N] staging blocks for ccka_get_trajectory
+  int64_t traj_stage = 0;       // their capacity in records (ccka_debug_traj_stage; 0: kTrajStageRecs)
   Buf<long long> d_parts;
   Buf<ccka_totals> d_totals;
   Buf<int32_t> d_sinq;
@@ -199,12 +200,17 @@ int dupload(ccka_ctx* c, ccka::DevBuf<T>& dst, const T* src, size_t count) {
 
 inline int64_t load_cols(const ccka_ctx* c) { return c->n_traces > 0 ? c->n_traces : c->N; }
 
+// block partials of the totals reduction (d_parts: 11 words each, then the overflow word)
+constexpr int kTotalsParts = 1024;
+
 // abi_ctx.cpp
 bool rules_fit_ring(const ccka_hpa_rules& r);
 int d1_prepare(ccka_ctx* c);
+int64_t carve_results(char* p, int64_t N, ccka::ResultPtrs* out);
 ccka::TableParams table_params(const ccka_ctx* c, const double* wc1000, int NW, int2* table, int32_t* jtab);
 // abi_rollout.cpp
 int setup_general(ccka_ctx* c, int32_t trajectory, ccka::KParams& k, int* block_out, size_t* lds_out);
+int totals_of(ccka_ctx* c, const ccka::ResultPtrs& res, int64_t N, ccka_totals* out);
 // abi_mlp.cpp
 int mlp_alloc(ccka_ctx* c, int64_t n);
 ccka::MlpParams mlp_params(const ccka_ctx* c, int64_t n, int tile);

@@ -2,8 +2,11 @@
 // its calls and can be told to fail the next k of them. Host only, built with
 // AddressSanitizer + UndefinedBehaviorSanitizer by `make devbuf-test`
 // (tests/test_devbuf.py): a leak, a double free or a use after free aborts it.
+// Also the pure host rules of host_rules.h (accepted trace generators, the
+// trajectory staging arithmetic), at the edge of every rule.
 #define CCKA_DEVBUF_NO_HIP
 #include "devbuf.h"
+#include "host_rules.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -169,7 +172,54 @@ static void test_move() {
   CHECK(empty(d) && empty(a));
 }
 
+// host_rules.h: the accepted trace generators at the edge of every rule, and
+// the staging arithmetic of the trajectory read-back (UBSan watches the sums)
+static ccka_trace_gen gen(int32_t blo, int32_t bhi, int32_t alo, int32_t ahi, int32_t noise, int32_t mult, int32_t len) {
+  ccka_trace_gen g{};
+  g.base_lo = blo; g.base_hi = bhi; g.amp_lo_pm = alo; g.amp_hi_pm = ahi;
+  g.noise_pm = noise; g.burst_prob_pm = 500; g.burst_mult_pm = mult; g.burst_len = len;
+  return g;
+}
+
+static void test_host_rules() {
+  using ccka::trace_gen_invalid;
+  CHECK(!trace_gen_invalid(gen(500, 5000, 200, 800, 50, 3000, 30)));
+  CHECK(!trace_gen_invalid(gen(0, 2000000000, 0, 3000, 1000, 3000, 30)));
+  CHECK(!trace_gen_invalid(gen(0, 2000000000, 0, 3000, -1000, -3000, 700)));
+  CHECK(!trace_gen_invalid(gen(7, 7, -5, -5, 0, 0, 0)));
+  CHECK(trace_gen_invalid(gen(10, 9, 0, 0, 0, 0, 0)) && trace_gen_invalid(gen(0, 0, 1, 0, 0, 0, 0)));
+  CHECK(!trace_gen_invalid(gen(-1, INT32_MAX - 2, 0, 0, 0, 0, 0)));  // width + 1 = INT32_MAX
+  CHECK(trace_gen_invalid(gen(-1, INT32_MAX - 1, 0, 0, 0, 0, 0)));
+  CHECK(trace_gen_invalid(gen(INT32_MIN, INT32_MAX, 0, 0, 0, 0, 0)));  // width + 1 = 2^32: a modulus of 0
+  CHECK(trace_gen_invalid(gen(0, 1, INT32_MIN, INT32_MAX, 0, 0, 0)));
+  CHECK(!trace_gen_invalid(gen(0, 1, 0, 0, 0, 0, INT32_MAX - 1439)) && trace_gen_invalid(gen(0, 1, 0, 0, 0, 0, INT32_MAX - 1438)));
+  CHECK(trace_gen_invalid(gen(0, 1, 0, 0, 0, 0, -1)));
+  // P1: 2^31 * (65536000 + 65536 A) <= 2^63 - 1  <=>  A <= 64536 (INT32_MIN as base: |base| = 2^31)
+  CHECK(!trace_gen_invalid(gen(INT32_MIN, INT32_MIN + 1, 0, 64535, 0, 0, 0)));
+  CHECK(trace_gen_invalid(gen(INT32_MIN, INT32_MIN + 1, 0, 64536, 0, 0, 0)));
+  CHECK(trace_gen_invalid(gen(INT32_MIN, INT32_MIN + 1, -64536, 0, 0, 0, 0)));
+  // P2: V1 = 8e9; 8e9 * (37837000 + 131072 n) <= 2^63 - 1  <=>  n <= 8507
+  CHECK(!trace_gen_invalid(gen(0, 2000000000, 0, 3000, 8507, 0, 0)) && trace_gen_invalid(gen(0, 2000000000, 0, 3000, -8508, 0, 0)));
+  CHECK(trace_gen_invalid(gen(0, 2000000000, 0, 3000, INT32_MIN, 0, 0)));
+  // P3: V2 = 8e9 * 168909000 div 37837000 = 35712979358; * m <= 2^63 - 1  <=>  m <= 258263863
+  CHECK(!trace_gen_invalid(gen(0, 2000000000, 0, 3000, 1000, 258263863, 0)));
+  CHECK(trace_gen_invalid(gen(0, 2000000000, 0, 3000, 1000, -258263864, 0)));
+  CHECK(trace_gen_invalid(gen(0, 2000000000, 0, 3000, 1000, INT32_MIN, 0)));
+
+  using ccka::traj_stage_cap;
+  const int64_t dflt = ccka::kTrajStageRecs;
+  CHECK(traj_stage_cap(203, 203 * 71, 0) == 203 * 71);          // a small trajectory: all of it
+  CHECK(traj_stage_cap(203, 203 * 71, 33 * 203) / 203 == 33);   // tc = 33
+  CHECK(traj_stage_cap(203, 203 * 71, 33 * 203 + 202) / 203 == 33);
+  CHECK(traj_stage_cap(203, 203 * 71, 5) == 203);               // never less than one step
+  CHECK(traj_stage_cap(203, 203 * 71, 1 << 30) == 203 * 71);    // never more than the trajectory
+  CHECK(traj_stage_cap(1000, dflt * 10, 0) == dflt && traj_stage_cap(dflt + 7, (dflt + 7) * 4, 0) == dflt + 7);
+  CHECK(ccka::trace_tile_count(65, 5, 64) == 5 * 128 && ccka::trace_tile_count(64, 5, 64) == 5 * 64);
+  CHECK(ccka::trace_nt_count(65, 5, 4) == 65 * 5 * 4);
+}
+
 int main() {
+  test_host_rules();
   test_reserve();
   test_resize();
   test_overflow();

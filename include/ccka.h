@@ -323,7 +323,22 @@ typedef struct ccka_sweep_stat {
   int32_t q_ppm[4];
 } ccka_sweep_stat;
 
-/* Synthetic load-trace generator (docs/SEMANTICS.md §4). */
+/* Synthetic load-trace generator (docs/SEMANTICS.md §4). ccka_gen_load accepts
+ * the parameters with which every intermediate of §4 stays inside the
+ * arithmetic that evaluates it, for every scenario, step and draw, and
+ * returns CCKA_EINVAL for the rest (there the values are undefined):
+ *  - base_lo <= base_hi and amp_lo_pm <= amp_hi_pm, each width + 1 <= INT32_MAX
+ *    (the modulus of the draw is formed in int32);
+ *  - 0 <= burst_len <= INT32_MAX - 1439 (bstart + burst_len is an int32 sum);
+ *  - with B = max |base|, A = max |amp| over the ranges, |SIN| <= 65536 and
+ *    |e| <= 131072, the worst case of each signed 64-bit product:
+ *      P1 = B * (65536000 + 65536 A)              <= INT64_MAX, V1 = P1 div 65536000
+ *      P2 = V1 * (37837000 + 131072 |noise_pm|)   <= INT64_MAX, V2 = P2 div 37837000
+ *      P3 = V2 * |burst_mult_pm|                  <= INT64_MAX
+ *    (e.g. base up to 2e9 with amplitude up to 3000, noise up to +-1000 and a
+ *    burst multiplier up to +-3000 permille lies well inside). Negative
+ *    amplitudes, noise and multipliers are allowed; the result is clamped to
+ *    [0, INT32_MAX]. */
 typedef struct ccka_trace_gen {
   uint64_t seed;
   int32_t base_lo, base_hi;       /* millicores */

@@ -1,13 +1,17 @@
 """GPU checks of the sweep tail statistics (docs/SEMANTICS.md 6): per-grid
 quantiles and tail sums from the device's radix select against the numpy
 restatement (tests/sweep_stat_ref.py) on adversarial keys and on a sweep's
-oracle results, SUM objectives against ccka_get_grid_stats bit for bit, and
-the frontier over the statistics, local and through a one-rank communicator."""
+oracle results, SUM objectives against ccka_get_grid_stats bit for bit, the
+sums and tail sums of doubles (signed ones included) bit for bit against the
+summation order SEMANTICS 6 states (tests/util_ref.py) and within the bound
+that holds for any order, and the frontier over the statistics, local and
+through a one-rank communicator."""
 import numpy as np
 import pytest
 
 import pyoracle as po
 import sweep_stat_ref as ref
+import util_ref as ur
 from ccka import abi, configs
 from ccka.engine import Engine
 from parity import oracle, run_engine
@@ -42,8 +46,10 @@ def _check(got, want, kinds):
 
 
 # ---- 1. selection on adversarial keys (no rollout) -----------------------
-def _columns(g, tail):
-    """Five grids of g scenarios whose keys stress every radix digit."""
+def _columns(g, tail, signed=False):
+    """Five grids of g scenarios whose keys stress every radix digit. signed
+    (with tail): the doubles keep their signs (held to the stated summation
+    order and the order-free bound below, not to TAIL_RTOL)."""
     rng = np.random.default_rng(1000 * g + tail)
     cost = np.empty((5, g), np.int64)
     cost[0] = np.array([I64.min, I64.max, 0, -1], np.int64)[rng.integers(0, 4, g)]
@@ -63,7 +69,8 @@ def _columns(g, tail):
     energy[:, 1:2 * h:2] = np.nextafter(energy[:, 0:2 * h:2], np.inf)              # pairs one ulp apart
     if tail:  # sums must stay inside int64; the double tolerance is for non-negative terms
         cost = np.clip(cost, -(1 << 40), 1 << 40)
-        gco2, energy = np.abs(gco2), np.abs(energy)
+        if not signed:
+            gco2, energy = np.abs(gco2), np.abs(energy)
     return {"cost_uphmin": cost.ravel(), "slo_minutes": slo.ravel(), "gco2": gco2.ravel(),
             "energy_wmin": energy.ravel()}
 
@@ -82,6 +89,57 @@ def test_selection_on_adversarial_keys(engine, g):
             if kind == ref.QUANTILE:  # always an element of the input
                 for f in ref.FIELDS:
                     assert all(v in cols[f].reshape(5, g)[i] for i, v in enumerate(got[f])), f
+
+
+# ---- 1b. the sums' order (SEMANTICS 6), signed doubles included ------------
+def _bits(a):
+    return np.asarray(a, np.float64).view(np.int64)
+
+
+def _within_fsum_bound(got, terms, what):
+    """|got - fsum(terms)| <= (n - 1) 2^-53 sum|terms|: holds for any order of the additions."""
+    exact, bound = ur.fsum_bound(terms)
+    print(what, "err", abs(got - exact), "bound", bound)
+    assert abs(got - exact) <= bound, (what, got, exact, bound)
+
+
+# 255 / 256 / 257: the strided loop's first wrap; 513, 1024, 2500: 3, 4 and 10 trips
+@pytest.mark.parametrize("signed", [False, True], ids=["nonneg", "signed"])
+@pytest.mark.parametrize("g", [1, 255, 256, 257, 513, 1024, 2500])
+def test_grid_sums_in_the_stated_order(engine, g, signed):
+    cols = _columns(g, True, signed)
+    got = engine.debug_grid_stat(cols["cost_uphmin"], cols["slo_minutes"], cols["gco2"], cols["energy_wmin"], g,
+                                 abi.sweep_stat())
+    assert len(got) == 5
+    assert np.array_equal(got["grid"], np.arange(5)) and np.array_equal(got["scenarios"], np.full(5, g))
+    for f in ("cost_uphmin", "slo_minutes"):  # Python ints: exact
+        rows = cols[f].reshape(5, g)
+        assert got[f].tolist() == [sum(r.tolist()) for r in rows], f
+    for f in ("gco2", "energy_wmin"):
+        rows = cols[f].reshape(5, g)
+        want = [ur.grid_sum(r) for r in rows]
+        assert np.array_equal(_bits(got[f]), _bits(want)), (f, got[f], want)  # bit for bit
+        for i, r in enumerate(rows):
+            _within_fsum_bound(float(got[f][i]), r, f"{f} sum g={g} grid {i}")
+
+
+@pytest.mark.parametrize("signed", [False, True], ids=["nonneg", "signed"])
+@pytest.mark.parametrize("g", [1, 2, 63, 64, 65, 257, 700, 1024, 1025, 2500])
+def test_tail_sums_in_the_stated_order(engine, g, signed):
+    cols = _columns(g, True, signed)
+    for q in (0, 1, 500000, 950000, 10**6):
+        got = engine.debug_grid_stat(cols["cost_uphmin"], cols["slo_minutes"], cols["gco2"], cols["energy_wmin"], g,
+                                     _stat(ref.TAIL, q))
+        want = ref.grid_stat(cols, g, [ref.TAIL] * 4, [q] * 4)
+        for f in ("grid", "scenarios", "cost_uphmin", "slo_minutes"):  # integers: exact
+            assert np.array_equal(got[f], want[f]), (f, q)
+        k = ref.rank(g, q)
+        for f in ("gco2", "energy_wmin"):
+            rows = cols[f].reshape(5, g)
+            stated = [ur.tail_sum(r, k) for r in rows]
+            assert np.array_equal(_bits(got[f]), _bits(stated)), (f, q, got[f], stated)  # bit for bit
+            for i, r in enumerate(rows):
+                _within_fsum_bound(float(got[f][i]), ur.tail_terms(r, k), f"{f} tail g={g} q={q} grid {i}")
 
 
 # ---- 2.-4., 6., 7. on one sweep -------------------------------------------
