@@ -450,7 +450,7 @@ static bool rules_ok(const ccka_hpa_rules& r) {
 int ccka_set_world(ccka_ctx* c, const ccka_world* w) {
   if (!c || !w) return CCKA_EINVAL;
   (void)hipSetDevice(c->device);
-  if (w->n_steps < 1 || w->n_steps > 65535) return fail(c, CCKA_EINVAL, "n_steps out of range");
+  if (const char* why = world_timing_invalid(*w)) return fail(c, CCKA_EINVAL, "%s", why);
   if (w->max_nodes < 1 || w->max_nodes > CCKA_MAX_NODES) return fail(c, CCKA_EINVAL, "max_nodes out of range");
   if (w->n_types < 1 || w->n_types > CCKA_MAX_TYPES || !w->types) return fail(c, CCKA_EINVAL, "catalog invalid");
   if (w->n_zones < 1 || w->n_zones > CCKA_MAX_ZONES) return fail(c, CCKA_EINVAL, "n_zones out of range");
@@ -461,7 +461,6 @@ int ccka_set_world(ccka_ctx* c, const ccka_world* w) {
   if (w->disrupt_ext & ~(CCKA_DISRUPT_DRIFT | CCKA_DISRUPT_REPLACE | CCKA_DISRUPT_MULTI))
     return fail(c, CCKA_EINVAL, "unknown disrupt_ext bits");
   if (w->base_type < 0 || w->base_type >= w->n_types) return fail(c, CCKA_EINVAL, "base_type out of range");
-  if (w->provision_delay_steps < 0 || w->start_minute < 0) return fail(c, CCKA_EINVAL, "negative timing");
   for (int k = 0; k < w->n_types; ++k) {
     const ccka_itype& t = w->types[k];
     if (t.vcpu < 0 || t.alloc_cpu_m <= 0 || t.alloc_mem_mi < 0 || t.max_pods < 0)

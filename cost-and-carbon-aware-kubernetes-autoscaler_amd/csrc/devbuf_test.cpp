@@ -3,7 +3,8 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer by `make devbuf-test`
 // (tests/test_devbuf.py): a leak, a double free or a use after free aborts it.
 // Also the pure host rules of host_rules.h (accepted trace generators, the
-// trajectory staging arithmetic), at the edge of every rule.
+// timing rules of a world, the trajectory staging arithmetic), at the edge of
+// every rule.
 #define CCKA_DEVBUF_NO_HIP
 #include "devbuf.h"
 #include "host_rules.h"
@@ -205,6 +206,31 @@ static void test_host_rules() {
   CHECK(!trace_gen_invalid(gen(0, 2000000000, 0, 3000, 1000, 258263863, 0)));
   CHECK(trace_gen_invalid(gen(0, 2000000000, 0, 3000, 1000, -258263864, 0)));
   CHECK(trace_gen_invalid(gen(0, 2000000000, 0, 3000, 1000, INT32_MIN, 0)));
+
+  // the timing rules of a world: the last accepted and the first rejected value of each
+  auto timing = [](int32_t T, int32_t start, int32_t delay, int32_t ps, int32_t pe) {
+    ccka_world w{};
+    w.n_steps = T; w.start_minute = start; w.provision_delay_steps = delay;
+    w.peak_start_min = ps; w.peak_end_min = pe;
+    return ccka::world_timing_invalid(w);
+  };
+  const int32_t sm = ccka::kMaxStartMinute, dm = ccka::kMaxProvisionDelay;
+  CHECK(sm == INT32_MAX - 65535 && dm == INT32_MAX - 65535);
+  CHECK(!timing(1440, 0, 1, 960, 1260));
+  CHECK(!timing(1, 0, 0, 0, 0) && timing(0, 0, 0, 0, 0));
+  CHECK(!timing(65535, 0, 0, 0, 0) && timing(65536, 0, 0, 0, 0));
+  CHECK(timing(10, -1, 0, 0, 0) && timing(10, 0, -1, 0, 0) && timing(10, INT32_MIN, 0, 0, 0) && timing(10, 0, INT32_MIN, 0, 0));
+  CHECK(!timing(65535, sm, 0, 0, 0) && timing(65535, sm + 1, 0, 0, 0) && timing(1, INT32_MAX, 0, 0, 0));
+  CHECK(!timing(65535, 0, dm, 0, 0) && timing(65535, 0, dm + 1, 0, 0) && timing(1, 0, INT32_MAX, 0, 0));
+  {
+    // what the bounds protect, formed as the kernels form it (UBSan watches the sums)
+    volatile int32_t s = sm, d = dm, t = 65535;
+    const int32_t minute = (s + t) % 1440, ready = (t - 1) + d;
+    CHECK(minute == (int32_t)(((int64_t)sm + 65535) % 1440) && ready == 0x7ffffffe);
+  }
+  CHECK(!timing(10, 0, 0, 0, 1440) && !timing(10, 0, 0, 1440, 0) && !timing(10, 0, 0, 1440, 1440));
+  CHECK(timing(10, 0, 0, -1, 0) && timing(10, 0, 0, 0, -1) && timing(10, 0, 0, 1441, 0) && timing(10, 0, 0, 0, 1441));
+  CHECK(timing(10, 0, 0, -560, 100) && timing(10, 0, 0, INT32_MIN, 0) && timing(10, 0, 0, 0, INT32_MAX));
 
   using ccka::traj_stage_cap;
   const int64_t dflt = ccka::kTrajStageRecs;

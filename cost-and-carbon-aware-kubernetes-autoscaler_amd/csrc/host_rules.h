@@ -1,7 +1,8 @@
 // host_rules.h — pure host arithmetic of libccka.so's C ABI that needs no
-// device: which trace generators ccka_gen_load accepts, and the block of steps
-// ccka_get_trajectory stages at a time. No HIP here, so the stand-alone host
-// test (devbuf_test.cpp) covers it too.
+// device: which trace generators ccka_gen_load accepts, the timing fields
+// ccka_set_world accepts, and the block of steps ccka_get_trajectory stages at
+// a time. No HIP here, so the stand-alone host test (devbuf_test.cpp) covers
+// it too.
 #pragma once
 #include <cstdint>
 
@@ -40,6 +41,37 @@ inline const char* trace_gen_invalid(const ccka_trace_gen& g) {
   if (P2 > lim) return "v * (37837000 + noise * e) can leave int64";
   const i128 V2 = P2 / 37837000;
   if (V2 * mag(g.burst_mult_pm, g.burst_mult_pm) > lim) return "v * burst_mult can leave int64";
+  return nullptr;
+}
+
+// Largest start_minute and provision_delay_steps of a world (n_steps <= 65535).
+//   start_minute: every engine forms start_minute + t in int32 before the
+//     % 1440, for steps t <= n_steps (rollout_kernel.h `(gw->start_minute + t)
+//     % 1440`, the policy features' lookahead `gw->start_minute + tq`, the
+//     oracle's `w->start_minute + t1`), so start_minute + 65535 <= INT32_MAX.
+//   provision_delay_steps: a node launched at step t <= n_steps - 1 <= 65534
+//     is ready at the int32 step t + delay (`nready[n] = t + delay`,
+//     `sready[n] = rs`, the oracle's `nd->ready_step`), and `next_ready` keeps
+//     the least of them with 0x7fffffff for "none pending": t + delay <=
+//     0x7ffffffe, so delay <= 0x7ffffffe - 65534. No kernel packs a ready step
+//     into fewer than 32 bits.
+// Both bounds are INT32_MAX - 65535.
+constexpr int32_t kMaxStartMinute = INT32_MAX - 65535;
+constexpr int32_t kMaxProvisionDelay = 0x7ffffffe - 65534;
+
+// nullptr when the timing fields of a world stay inside the arithmetic above
+// and the peak window is one of the day's: peak_start_min and peak_end_min in
+// [0, 1440] (1440: "to the end of the day" under `minute >= ps && minute <
+// pe`; the single-deployment kernel's next-edge distance `(ps % 1440 - minute
+// + 1439) % 1440 + 1` is positive only for ps % 1440 >= 0). Else the rule
+// that fails.
+inline const char* world_timing_invalid(const ccka_world& w) {
+  if (w.n_steps < 1 || w.n_steps > 65535) return "n_steps out of range";
+  if (w.start_minute < 0 || w.provision_delay_steps < 0) return "negative timing";
+  if (w.start_minute > kMaxStartMinute) return "start_minute + n_steps can leave int32";
+  if (w.provision_delay_steps > kMaxProvisionDelay) return "a ready step t + provision_delay_steps can reach 0x7fffffff";
+  if (w.peak_start_min < 0 || w.peak_start_min > 1440) return "peak_start_min outside [0, 1440]";
+  if (w.peak_end_min < 0 || w.peak_end_min > 1440) return "peak_end_min outside [0, 1440]";
   return nullptr;
 }
 

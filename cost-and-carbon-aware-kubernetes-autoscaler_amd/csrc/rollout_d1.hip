@@ -1707,6 +1707,10 @@ __global__ void __launch_bounds__(256, OCC) rollout_d1_kernel(D1Params p) {
                   flags |= 2u | 32u;
                   deleted++;
                   g_acted = true;
+                  // the source is tainted from here on: its free space leaves F
+                  // (the later pools of this step and every step until the
+                  // replacement is ready read it)
+                  ffree_now();
                   break;
                 }
               }

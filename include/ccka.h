@@ -148,11 +148,21 @@ typedef struct ccka_deployment {
   ccka_hpa_rules down;
 } ccka_deployment;
 
-/* Everything batch-uniform. Array pointers are HOST pointers. */
+/* Everything batch-uniform. Array pointers are HOST pointers.
+   Timing rules (ccka_set_world returns CCKA_EINVAL outside them; SEMANTICS 1):
+     1 <= n_steps <= 65535
+     0 <= start_minute <= INT32_MAX - 65535: start_minute + t stays an int32 for
+       every step; the minute of step t is (start_minute + t) mod 1440
+     0 <= provision_delay_steps <= INT32_MAX - 65535: every ready step
+       t + provision_delay_steps stays an int32 below 0x7fffffff; a delay
+       >= n_steps is valid (no launched node becomes ready)
+     0 <= peak_start_min, peak_end_min <= 1440: the window [start, end) of the
+       day's minutes, wrapping midnight when start > end; 1440 is the end of
+       the day, start == end the empty window */
 typedef struct ccka_world {
-  int32_t n_steps;
-  int32_t start_minute;
-  int32_t provision_delay_steps;
+  int32_t n_steps;              /* 1 .. 65535 */
+  int32_t start_minute;         /* 0 .. INT32_MAX - 65535 */
+  int32_t provision_delay_steps;/* 0 .. INT32_MAX - 65535 */
   int32_t max_nodes;            /* Karpenter node slots per scenario (<= 16) */
 
   int32_t n_types;
@@ -174,8 +184,8 @@ typedef struct ccka_world {
   double base_util;
   double carbon_weight;         /* $/kgCO2 (default; per-scenario override) */
   int32_t pdb_min_available_pct;/* -1 none */
-  int32_t peak_start_min;
-  int32_t peak_end_min;
+  int32_t peak_start_min;       /* 0 .. 1440 */
+  int32_t peak_end_min;         /* 0 .. 1440 */
   int32_t peak_switch;          /* 1: peak/off-peak switch on            */
   int32_t reset_ca_s;           /* consolidateAfter of the RESET profile */
   int32_t disrupt_ext;          /* CCKA_DISRUPT_* bits: Karpenter disruption

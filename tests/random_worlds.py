@@ -25,6 +25,14 @@ catalogs of 63-200 types, 1-8 regions laid out over three workgroups of 600
 scenarios, 3-4 pools, 9-16 slots, shared traces, 8 carbon weights / zone
 masks. Their sub-kinds are chosen by the seed (seed % 3, seed % 4, ...), so
 how many worlds take each kernel path is fixed, not a matter of luck.
+
+The time-axis kinds (TIMINGS; draw(profile, seed, timing=kind), seeds from
+timing_seeds) keep a profile's builders and replace the time axis: horizons of
+1-61, 1500-3000 and 65535 steps, every shape of the peak window, delays up to
+the last value ccka_set_world accepts, consolidateAfter beyond the horizon
+(_timing_kind, _timing_post). They draw from a stream of their own, so the
+worlds of draw(profile, seed) are what they were before the kinds existed
+(world_digest; tests/test_random_worlds.py freezes a few).
 """
 from __future__ import annotations
 
@@ -211,6 +219,173 @@ def _timing(rng):
     return (T, start, edge, other) if rng.integers(2) else (T, start, other, edge)
 
 
+# the time-axis kinds (draw(profile, seed, timing=kind)): what _timing never draws
+TIMINGS = ("days", "window", "short", "delay", "max")
+TIMING_PROFILES = ("d1_default", "d1_rules", "d1_sync15", "d1_keda", "d1_disrupt", "gk_single", "gk_multi", "sk", "loop")
+SHORT_T = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 59, 60, 61)
+# the last values ccka_set_world accepts (csrc/host_rules.h world_timing_invalid)
+MAX_START = 2**31 - 1 - 65535
+MAX_DELAY = 2**31 - 1 - 65535
+WINDOW_CHANGES = (0, 0, 2, 2, 0, 1, 0, 2, 2, 2)  # PEAK-flag changes of a switching scenario, by sub-kind
+CA_BEYOND_T = 4_000_000  # seconds: 66667 steps, more than any horizon (and than 0xFFFF)
+
+
+# days: per profile the first seeds from 0 upward (four for loop) whose oracle
+# run shows at a step >= 1440 a launch (flags bit 1), a deletion (bit 2) and a
+# change of the PEAK flag in a switching scenario (tests/test_random_worlds.py
+# asserts it; a generator change that moves these worlds fails there). Among
+# the eight of d1_disrupt (1, 22) and gk_multi (2, 5) two also show a drift
+# record (bit 4) that late.
+DAYS_SEEDS = {
+    "d1_default": (2, 3, 8, 10, 13, 18, 19, 21),
+    "d1_rules": (1, 3, 5, 7, 10, 16, 18, 23),
+    "d1_sync15": (1, 2, 6, 8, 9, 10, 12, 17),
+    "d1_keda": (0, 1, 2, 3, 4, 5, 6, 7),
+    "d1_disrupt": (1, 3, 8, 10, 13, 21, 22, 26),
+    "gk_single": (1, 6, 12, 13, 14, 15, 18, 19),
+    "gk_multi": (1, 2, 5, 8, 9, 10, 11, 12),
+    "sk": (1, 2, 3, 6, 7, 9, 10, 12),
+    "loop": (13, 14, 36, 48),
+}
+MAX_PROFILES = ("d1_default", "d1_sync15", "gk_single", "sk")
+
+
+def timing_seeds(profile, kind):
+    """The worlds of a time-axis kind: draw(profile, seed, timing=kind) for these seeds."""
+    if kind == "days":
+        return DAYS_SEEDS[profile]
+    if kind == "max":
+        return (0,) if profile in MAX_PROFILES else ()
+    return range({"window": 20, "short": len(SHORT_T), "delay": 16}[kind])
+
+
+def pend_limit_world(n=N_SCEN):
+    """One HPA deployment pinned at 32767 replicas for 65535 steps, no node
+    ever ready (delay = T): pending_pod_minutes = 32767 x 65535 =
+    2 147 385 345 in every scenario, 98 303 below 2^31, the most the
+    single-deployment engine admits (D1_REC_SAT pods, n_steps <= 65535)."""
+    rng = np.random.default_rng([20251205, 97, 0])
+    cat, R, Z = _geo(rng)
+    dep = deployment(abi.SCALER_HPA, replicas0=32767, min_r=32767, max_r=32767, target=70, req_cpu=100, req_mem=64,
+                     limit_cpu=0, cap_sel=3, pdb=0)
+    spec = _world(rng, [dep], _pools(rng, Z, 2), cat, R, Z, 8, timing=("max", 0, False))
+    spec.base_nodes, spec.provision_delay_steps = 0, spec.n_steps
+    sc = _scenarios(rng, R, (0, 60, 300), n=n)
+    sc.max_replicas = None
+    return spec, sc, np.zeros((spec.n_steps, 1, n), np.int32)
+
+
+def ca_limit_world(ca_s=CA_BEYOND_T, n=N_SCEN):
+    """The d1_default world of the last accepted horizon with ca_s as every
+    pool's consolidateAfter under every profile and no load after step 64:
+    the nodes of the first burst stand empty for the remaining 65470 steps.
+    At CA_BEYOND_T (66667 steps; the single-deployment kernel clamps its
+    copy to 65535, which no node launched at t >= 0 reaches before T) none is
+    ever deleted; at 32767 steps they all are (the CPU guard asserts both)."""
+    spec, sc, load = draw("d1_default", 0, timing="max")
+    for p in spec.pools:
+        p.base.consolidate_after_s = ca_s
+        for prof in range(3):
+            p.profile[prof].consolidate_after_s = -1
+    load = load.copy()
+    load[64:] = 0
+    return spec, sc, load
+
+
+def _outside(rng, start, T):
+    """A minute outside [start, start + T] (T <= 400)."""
+    return (start + T + int(rng.integers(30, 1440 - T - 30))) % 1440
+
+
+def _timing_kind(rng, kind, seed, loop=False):
+    """(n_steps, start_minute, peak_start, peak_end, delay or None) of a
+    time-axis kind; delay None keeps the profile's own draw (0-3 steps).
+
+    days    1500-3000 steps (loop: 1500-1800) from any minute, any window of
+            30-1410 minutes: 2-4 edges, half of the windows wrap midnight
+    window  150-400 steps, the window's shape by seed % 10 (WINDOW_CHANGES)
+    short   SHORT_T[seed] steps, a clock hour at t = 1 (even seeds) or t = T - 1
+            (odd), delay in {0, 1, T - 1, T, T + 1}
+    delay   200-300 steps, delay = (5, 59, 60, 61, T - 1, T, T + 1, MAX_DELAY)[seed % 8]
+    max     65535 steps from start minute MAX_START"""
+    if kind == "days":
+        T = int(rng.integers(1500, 1801 if loop else 3001))
+        start, ps = int(rng.integers(0, 1440)), int(rng.integers(0, 1440))
+        return T, start, ps, (ps + int(rng.integers(30, 1411))) % 1440, None
+    if kind == "max":
+        ps = int(rng.integers(0, 1440))
+        return 65535, MAX_START, ps, (ps + int(rng.integers(30, 1411))) % 1440, None
+    if kind == "short":
+        T = SHORT_T[seed]
+        hour = 60 * int(rng.integers(0, 24))
+        start = (hour - (1 if seed % 2 == 0 else T - 1)) % 1440
+        edge = (start + int(rng.integers(0, T + 1))) % 1440
+        other = int(rng.integers(0, 1440))
+        ps, pe = (edge, other) if rng.integers(2) else (other, edge)
+        return T, start, ps, pe, pick(rng, [0, 1, T - 1, T, T + 1])
+    if kind == "delay":
+        T = int(rng.integers(200, 301))
+        start = int(rng.integers(0, 1440))
+        edge, other = (start + int(rng.integers(20, T - 19))) % 1440, _outside(rng, start, T)
+        ps, pe = (edge, other) if rng.integers(2) else (other, edge)
+        return T, start, ps, pe, (5, 59, 60, 61, T - 1, T, T + 1, MAX_DELAY)[seed % 8]
+    assert kind == "window", kind
+    T = int(rng.integers(150, 401))
+    start = int(rng.integers(0, 1440))
+    sub = seed % 10
+    at = lambda t: (start + t) % 1440  # the minute of step t
+    if sub == 0:
+        ps = pe = int(rng.integers(0, 1441))
+    elif sub == 1:
+        ps, pe = 0, 1440
+    elif sub in (2, 3):  # midnight at step a, the window opens at step b < a
+        a = int(rng.integers(40, T - 39))
+        start = 1440 - a
+        ps = start + int(rng.integers(10, a - 9))
+        pe = 1440 if sub == 2 else int(rng.integers(5, T - a - 4))  # closes at step a + pe < T
+    elif sub == 4:
+        ps, pe = (start, _outside(rng, start, T)) if rng.integers(2) else (_outside(rng, start, T), start)
+    elif sub in (5, 6):
+        edge = at(T - 1 if sub == 5 else T)
+        ps, pe = (edge, _outside(rng, start, T)) if rng.integers(2) else (_outside(rng, start, T), edge)
+    elif sub == 7:  # two of the clock hours inside the horizon
+        first = 60 - start % 60
+        j = rng.choice((T - 1 - first) // 60 + 1, size=2, replace=False)
+        ps, pe = at(first + 60 * int(j[0])), at(first + 60 * int(j[1]))
+    elif sub == 8:
+        ps = at(int(rng.integers(5, T - 5)))
+        pe = ps + 1  # (1439 -> 1440: the end of the day)
+    else:
+        b = int(rng.integers(5, T - 124))
+        ps, pe = at(b), at(b + int(rng.integers(61, 121)))
+        if rng.integers(2):
+            ps, pe = pe, ps
+        start += 1440 * int(rng.integers(1, 1001))
+    return T, start, ps, pe, None
+
+
+def _timing_post(spec, sc, kind, seed, profile):
+    """consolidateAfter beyond the horizon. delay, seeds 8-15: 3600 s or
+    86400 s in pool 0's PEAK or OFFPEAK patch (odd seeds: as the world's
+    reset_ca_s, no per-scenario override); seeds 8 and 11 (small delays, so
+    nodes get ready and idle): CA_BEYOND_T, more than 65535 steps. max,
+    d1_default: pool 0 keeps CA_BEYOND_T under every profile, so a node idle
+    for 32768 steps and more stays."""
+    p0 = spec.pools[0]
+    if kind == "delay" and seed >= 8:
+        ca = CA_BEYOND_T if seed in (8, 11) else (3600, 86400)[(seed // 2) % 2]
+        if seed % 2:
+            spec.reset_ca_s, sc.reset_ca_s = ca, None
+            if p0.profile[abi.PROFILE_RESET].consolidate_after_s < 0:
+                p0.profile[abi.PROFILE_RESET].consolidate_after_s = 0  # RESET sets it: reset_ca_s applies
+        else:
+            p0.profile[(abi.PROFILE_PEAK, abi.PROFILE_OFFPEAK)[(seed // 4) % 2]].consolidate_after_s = ca
+    if kind == "max" and profile == "d1_default":
+        p0.base.consolidate_after_s = CA_BEYOND_T
+        for prof in range(3):
+            p0.profile[prof].consolidate_after_s = -1
+
+
 def _scenarios(rng, R, stab_set, cap_set=(1, 2, 3), switch_p=0.85, n=N_SCEN):
     kw = {}
     if rng.random() < 0.6:
@@ -234,15 +409,23 @@ def _scenarios(rng, R, stab_set, cap_set=(1, 2, 3), switch_p=0.85, n=N_SCEN):
 
 
 def _load(rng, T, his, n=N_SCEN):
-    """[T][D][n] piecewise-constant bursts, one column per (deployment, scenario)."""
+    """[T][D][n] piecewise-constant bursts, one column per (deployment, scenario).
+    O(T D n) in memory: the segment of step t is the number of segment ends
+    <= t, found per column by a binary search (a horizon of 65535 steps fits)."""
     D = len(his)
     S = T // 10 + 1
     ends = np.cumsum(rng.integers(10, 41, size=(D, n, S)), axis=2)
-    seg = (ends[None] <= np.arange(T)[:, None, None, None]).sum(axis=3)          # [T][D][n]
+    steps = np.arange(T)
+    seg = np.empty((D, n, T), np.int64)                                          # < S: ends[..., S - 1] >= 10 S > T
+    for d in range(D):
+        for i in range(n):
+            seg[d, i] = np.searchsorted(ends[d, i], steps, side="right")
     frac = rng.choice(np.array([0.0, 0.125, 0.5, 1.0]), size=(D, n, S))
-    lvl = np.take_along_axis(np.broadcast_to(frac[None], (T, D, n, S)), seg[..., None], axis=3)[..., 0]
-    lvl = lvl * np.asarray(his, np.float64)[None, :, None]
+    lvl = np.ascontiguousarray(np.take_along_axis(frac, seg, axis=2).transpose(2, 0, 1))  # [T][D][n]
+    del seg
+    lvl *= np.asarray(his, np.float64)[None, :, None]
     load = np.rint(lvl * (1.0 + 0.05 * rng.uniform(-1, 1, size=lvl.shape))).astype(np.int32)
+    del lvl
     if rng.integers(4) == 0:  # the int64 utilisation path and negative samples
         edge = rng.random(size=load.shape) < 0.01
         vals = rng.choice(np.array([-5000, 2_000_000_000, 2**31 - 1], np.int32), size=load.shape)
@@ -250,16 +433,19 @@ def _load(rng, T, his, n=N_SCEN):
     return np.ascontiguousarray(load, np.int32)
 
 
-def _world(rng, deploys, pools, cat, R, Z, max_nodes, **kw):
-    T, start, ps, pe = _timing(rng)
+def _world(rng, deploys, pools, cat, R, Z, max_nodes, timing=None, **kw):
+    T, start, ps, pe, delay = _timing(rng) + (None,) if timing is None else _timing_kind(rng, *timing)
     prices = _prices_wide if cat.k > 6 else _prices
-    return WorldSpec(catalog=cat, ci=rng.uniform(50.0, 700.0, size=(R, 24)), price=prices(rng, cat, R, Z),
+    spec = WorldSpec(catalog=cat, ci=rng.uniform(50.0, 700.0, size=(R, 24)), price=prices(rng, cat, R, Z),
                      pools=pools, deploys=deploys, n_steps=T, start_minute=start,
                      provision_delay_steps=pick(rng, [0, 1, 1, 1, 2, 3]), max_nodes=max_nodes,
                      base_nodes=int(rng.integers(0, 4)), base_util=pick(rng, [0.0, 0.25]),
                      slo_util_pct=pick(rng, [100, 150]), pdb_pct=pick(rng, [-1, -1, 0, 50, 50, 80]),
                      peak_start=ps, peak_end=pe, peak_switch=1, reset_ca_s=pick(rng, [0, 30, 90]),
                      carbon_weight=pick(rng, [0.0, 0.5, 2.0]), **kw)
+    if delay is not None:
+        spec.provision_delay_steps = delay
+    return spec
 
 
 def _geo(rng):
@@ -272,7 +458,7 @@ HIS = [3000, 9000, 20000]
 # ---------------------------------------------------------------------------
 # profiles
 # ---------------------------------------------------------------------------
-def _d1(rng, kind, n=N_SCEN):
+def _d1(rng, kind, n=N_SCEN, timing=None):
     cat, R, Z = _geo(rng)
     hi = pick(rng, HIS)
     kw = {}
@@ -297,12 +483,12 @@ def _d1(rng, kind, n=N_SCEN):
         on = int(rng.integers(1, 8)) if kind == "d1_disrupt" else 1
         kw.update(drift=on & 1, replace=(on >> 1) & 1, multi=(on >> 2) & 1)
     pools = _pools(rng, Z, int(rng.integers(1, 3)), disrupt=disrupt)
-    spec = _world(rng, [dep], pools, cat, R, Z, int(rng.integers(3, 9)), **kw)
+    spec = _world(rng, [dep], pools, cat, R, Z, int(rng.integers(3, 9)), timing=timing, **kw)
     sc = _scenarios(rng, R, stab_set, cap_set, switch_p=0.95 if disrupt else 0.85, n=n)
     return spec, sc, _load(rng, spec.n_steps, [hi], n)
 
 
-def _gk_single(rng, geo=None, n=N_SCEN):
+def _gk_single(rng, geo=None, n=N_SCEN, timing=None):
     cat, R, Z = geo or _geo(rng)
     hi = pick(rng, HIS)
     why = pick(rng, ["pool_limit", "slots_drift", "policies3", "window", "sync30"])
@@ -331,14 +517,14 @@ def _gk_single(rng, geo=None, n=N_SCEN):
         kw.update(drift=on & 1, replace=(on >> 1) & 1, multi=(on >> 2) & 1)
     disrupt = bool(kw.get("drift") or kw.get("replace") or kw.get("multi"))
     pools = _pools(rng, Z, int(rng.integers(1, 4)), disrupt=disrupt, limits=why == "pool_limit")
-    spec = _world(rng, [dep], pools, cat, R, Z, slots, **kw)
+    spec = _world(rng, [dep], pools, cat, R, Z, slots, timing=timing, **kw)
     sc = _scenarios(rng, R, stab_set, n=n)
     if why == "slots_drift" and sc.peak_switch is not None:
         sc.peak_switch[0] = 1  # one switching scenario: drift is not inert
     return spec, sc, _load(rng, spec.n_steps, [hi], n)
 
 
-def _gk_multi(rng, geo=None, n=N_SCEN):
+def _gk_multi(rng, geo=None, n=N_SCEN, timing=None):
     cat, R, Z = geo or _geo(rng)
     on = int(rng.integers(0, 8))
     kw = dict(drift=on & 1, replace=(on >> 1) & 1, multi=(on >> 2) & 1)
@@ -367,20 +553,20 @@ def _gk_multi(rng, geo=None, n=N_SCEN):
                 deploys.append(keda_trigger(pick(rng, [300, 700, 2000]), pick(rng, [0, 200, hi // 8 + hi // 20])))
                 his.append(hi)
     pools = _pools(rng, Z, int(rng.integers(1, 4)), disrupt=disrupt, limits=rng.integers(3) == 0)
-    spec = _world(rng, deploys, pools, cat, R, Z, int(rng.integers(8, 17)), **kw)
+    spec = _world(rng, deploys, pools, cat, R, Z, int(rng.integers(8, 17)), timing=timing, **kw)
     sc = _scenarios(rng, R, (0, 60, 300, 480), (2, 3, 3) if disrupt else (1, 2, 3), switch_p=0.95 if disrupt else 0.85,
                     n=n)
     return spec, sc, _load(rng, spec.n_steps, his, n)
 
 
-def _sk(rng, geo=None, n=N_SCEN, slots=None):
+def _sk(rng, geo=None, n=N_SCEN, slots=None, timing=None):
     cat, R, Z = geo or _geo(rng)
     n_dep = int(rng.integers(2, 5))
     kinds = ["hpa", "hpa"] + [pick(rng, ["hpa", "static"]) for _ in range(n_dep - 2)]
     deploys = [_hpa(rng, rules=pick(rng, ["default", "ring"]), stab_set=(0, 60, 300, 480), tol_set=(0.1, 0.0, 0.25, 0.05))
                if k == "hpa" else _static(rng) for k in (kinds[i] for i in rng.permutation(n_dep))]
     pools = _pools(rng, Z, int(rng.integers(1, 3)), limits=rng.integers(3) == 0)
-    spec = _world(rng, deploys, pools, cat, R, Z, slots or pick(rng, [8, 16]), hpa_sync_s=pick(rng, [0, 60]))
+    spec = _world(rng, deploys, pools, cat, R, Z, slots or pick(rng, [8, 16]), timing=timing, hpa_sync_s=pick(rng, [0, 60]))
     sc = _scenarios(rng, R, (0, 60, 300, 480), n=n)
     return spec, sc, _load(rng, spec.n_steps, [pick(rng, HIS) for _ in deploys], n)
 
@@ -603,11 +789,18 @@ def _sk_wide(rng, seed):
     return _finish_wide(rng, seed, _sk(rng, geo=(cat, R, Z), n=N_WIDE, slots=(8, 16)[(seed // 4) % 2]), R, layout)
 
 
-def draw(profile: str, seed: int, n: int = N_SCEN):
+def draw(profile: str, seed: int, n: int = N_SCEN, timing: str | None = None):
     """(WorldSpec, ScenarioSet, load [T][D][n] int32) of a profile's world
     number `seed`. n: the scenario count of the `loop` profile's worlds (130;
-    600 for several workgroups); the wide profiles fix their own."""
-    rng = np.random.default_rng([20251205, _PIDX[profile], seed])
+    600 for several workgroups); the wide profiles fix their own. timing: one
+    of TIMINGS in place of _timing's draw (a world stream of its own: the
+    profile's builders, another time axis; TIMING_PROFILES only)."""
+    if timing is None:
+        rng, tm = np.random.default_rng([20251205, _PIDX[profile], seed]), None
+    else:
+        assert profile in TIMING_PROFILES and timing in TIMINGS, (profile, timing)
+        rng = np.random.default_rng([20251205, _PIDX[profile], seed, 1 + TIMINGS.index(timing)])
+        tm = (timing, seed, profile == "loop")
     if profile == "d1_wide":
         return _d1_wide(rng, seed)
     if profile == "gk_wide":
@@ -615,16 +808,46 @@ def draw(profile: str, seed: int, n: int = N_SCEN):
     if profile == "sk_wide":
         return _sk_wide(rng, seed)
     if profile.startswith("d1_"):
-        return _d1(rng, profile)
-    if profile == "gk_single":
-        return _gk_single(rng)
-    if profile == "gk_multi":
-        return _gk_multi(rng)
-    if profile == "sk":
-        return _sk(rng)
-    if profile == "loop":
-        return _d1(rng, "d1_default" if seed % 2 == 0 else "loop_drift", n)
-    raise KeyError(profile)
+        world = _d1(rng, profile, timing=tm)
+    elif profile == "gk_single":
+        world = _gk_single(rng, timing=tm)
+    elif profile == "gk_multi":
+        world = _gk_multi(rng, timing=tm)
+    elif profile == "sk":
+        world = _sk(rng, timing=tm)
+    elif profile == "loop":
+        world = _d1(rng, "d1_default" if seed % 2 == 0 else "loop_drift", n, timing=tm)
+    else:
+        raise KeyError(profile)
+    if tm:
+        _timing_post(world[0], world[1], timing, seed, profile)
+    return world
+
+
+def world_digest(world) -> str:
+    """sha256 over everything of a world that reaches an engine: the spec's
+    scalar fields, catalog, tiles, pools and deployments, every scenario
+    array, and the load bytes."""
+    import dataclasses
+    import hashlib
+    spec, sc, load = world
+    h = hashlib.sha256()
+    for f in dataclasses.fields(spec):
+        v = getattr(spec, f.name)
+        if isinstance(v, (int, float, str)):
+            h.update(f"{f.name}={v!r};".encode())
+    cat = spec.catalog
+    h.update(",".join(cat.names).encode())
+    for a in (cat.vcpu, cat.mem_gib, cat.max_pods, cat.od_uph, spec.ci, spec.price):
+        h.update(str(a.dtype).encode() + str(a.shape).encode() + np.ascontiguousarray(a).tobytes())
+    for x in list(spec.pools) + list(spec.deploys):
+        h.update(bytes(x))
+    h.update(f"{sc.n},{sc.first_id},{sc.n_traces};".encode())
+    for name in sc._DT:
+        a = getattr(sc, name)
+        h.update(name.encode() + (b"-" if a is None else str(a.dtype).encode() + np.ascontiguousarray(a).tobytes()))
+    h.update(str(load.dtype).encode() + str(load.shape).encode() + np.ascontiguousarray(load).tobytes())
+    return h.hexdigest()
 
 
 def limit_world(which: str):

@@ -146,8 +146,8 @@ def check_world(engine, profile, seed, world=None, modes=None):
         _named(what, lambda: compare(rg, rc, tg, tc))
 
 
-def check_loop(engine, seed, launched, n=rw.N_SCEN):
-    spec, sc, load = rw.draw("loop", seed, n)
+def check_loop(engine, seed, launched, n=rw.N_SCEN, world=None):
+    spec, sc, load = world or rw.draw("loop", seed, n)
     ws, bs = configs.mlp_weights(seed)
     engine.set_world(spec)
     engine.set_scenarios(sc)

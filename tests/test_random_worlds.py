@@ -16,7 +16,22 @@ two CPU restatements agree on its worlds.
    launches in three regions, shared-trace worlds whose scenarios differ on
    one trace), and the spec model on seeds 0-9, first and last 8 scenarios.
 
-Run time of this file: 30 s before the wide profiles, 51 s with them (8 oracle threads)."""
+4. The time-axis kinds (random_worlds.TIMINGS; run on the GPU by
+   tests/test_gpu_time_axis.py): the oracle shows what each kind is drawn
+   for. days: a launch, a deletion and a PEAK-flag change at a step >= 1440 in
+   every frozen world, 2-4 window edges, late drift in two worlds of
+   d1_disrupt and gk_multi; window: the exact number of PEAK-flag changes of
+   every switching scenario by sub-kind; short: the clock hour where the start
+   minute puts it; delay: no pod ever runs where the delay is >= T; the
+   activity floors over the window and delay worlds; spec_model on the first
+   three scenarios of every days, window and short world inside its scope
+   (the days worlds one case each).
+   A few digests of the earlier profiles' worlds are frozen: the generator's
+   time-axis argument and its O(T D n) load construction moved none of them.
+
+Run time of this file (8 oracle threads): 30 s before the wide profiles, 51 s
+with them, about 7 min with the time-axis kinds (290 s of it
+tests/spec_model.py on the 56 days worlds inside its scope)."""
 import functools
 
 import numpy as np
@@ -208,3 +223,209 @@ def test_limit_worlds_are_at_the_limits():
             assert len(np.unique(sc.carbon_weight)) == 8, which  # kind 2: at the weight limit as well
         else:
             assert len(masks) <= 8, (which, masks)
+
+
+# ---------------------------------------------------------------------------
+# time-axis kinds
+# ---------------------------------------------------------------------------
+def test_earlier_worlds_did_not_move():
+    """sha256 of six worlds as the generator drew them before it had a timing
+    argument (spec, scenario arrays, load bytes)."""
+    want = {("d1_default", 0): "8ce8be91c1760da79acd515e817e450d24eb8320611d4b35dc0d1eabd897e0b9",
+            ("gk_multi", 7): "8113649f0d55704102f2e623055a3b5357e02a0403484d030ff248da80eb5625",
+            ("sk", 9): "2fac21d1c8d51e7b9d99f0f5cb29c0e4245fd8a0a7f0bfed93685b2a4c006205",
+            ("loop", 1): "17c15b453ae5e15f858f4b0217a026c34754c5e4fc66ff73c22f7dd497a4a236",
+            ("sk_wide", 3): "19b35ce4ddf99fd0ccf24b964dfaa9cca9c34f45ddaa8f06ed9f036072dc9824",
+            ("d1_wide", 4): "fe1792a5892c515f8f9d2807cfa0937bbc0b5aa1cc6fceda366486f6ba903680"}
+    got = {k: rw.world_digest(rw.draw(*k)) for k in want}
+    assert got == want
+
+
+def in_window(spec, minute):
+    ps, pe = spec.peak_start, spec.peak_end
+    return ps <= minute < pe if ps <= pe else (minute >= ps or minute < pe)
+
+
+@functools.lru_cache(maxsize=None)
+def timing_rows(profile, kind):
+    """The oracle's view of a kind's worlds of one profile (computed once, read-only)."""
+    rows = []
+    for seed in rw.timing_seeds(profile, kind):
+        spec, sc, load = rw.draw(profile, seed, timing=kind)
+        res, tr, det = po.rollout(spec, sc, load, traj=True, threads=THREADS, detail=True)
+        f = tr["flags"]
+        sw = np.ones(sc.n, bool) if sc.peak_switch is None else sc.peak_switch != 0
+        pk = (f & 1)[:, sw].astype(np.int8)
+        late = f[1440:]
+        rows.append(dict(
+            seed=seed, spec=spec, T=spec.n_steps, switching=int(sw.sum()),
+            launch=bool(res["launches"].sum() > 0), delete=bool(res["deletions"].sum() > 0),
+            changes=np.abs(np.diff(pk, axis=0)).sum(axis=0), pk_any=bool(pk.any()), pk_all=bool(pk.all()),
+            pk0=pk[0], pk_quiet=bool((f & 1)[:, ~sw].any()),
+            late_launch=bool((late & 2).any()), late_delete=bool((late & 4).any()), late_drift=bool((late & 16).any()),
+            late_change=bool(np.diff(pk[1439:], axis=0).any()) if spec.n_steps > 1440 else False,
+            running=int((tr["replicas"] - tr["pending"]).sum()), ready=int(det["ready"].sum()),
+            pend_min=int(res["pending_pod_minutes"].sum()), deletions=int(res["deletions"].sum())))
+    return rows
+
+
+@pytest.mark.parametrize("profile", rw.TIMING_PROFILES)
+def test_days_worlds_are_active_after_a_day(profile):
+    rows = timing_rows(profile, "days")
+    assert len(rows) == (4 if profile == "loop" else 8)
+    for r in rows:
+        what = f"{profile} days seed {r['seed']}"
+        assert 1500 <= r["T"] <= (1800 if profile == "loop" else 3000), what
+        assert r["late_launch"] and r["late_delete"] and r["late_change"], f"{what}: {r}"
+        assert r["switching"] and 2 <= r["changes"].min() and r["changes"].max() <= 4, f"{what}: {r['changes']}"
+        assert not r["pk_quiet"], what  # a scenario that does not switch never shows PEAK
+    if profile in ("d1_disrupt", "gk_multi"):
+        assert sum(r["late_drift"] for r in rows) >= 2, [r["late_drift"] for r in rows]
+    # half of the windows wrap midnight (over all profiles: test below)
+
+
+def test_days_windows_wrap_midnight_in_half_the_worlds():
+    wraps = [r["spec"].peak_start > r["spec"].peak_end for p in rw.TIMING_PROFILES for r in timing_rows(p, "days")]
+    assert 0.3 <= sum(wraps) / len(wraps) <= 0.7, sum(wraps)
+
+
+@pytest.mark.parametrize("profile", rw.TIMING_PROFILES)
+def test_window_shapes_change_the_peak_flag_as_stated(profile):
+    rows = timing_rows(profile, "window")
+    assert len(rows) == 20
+    for r in rows:
+        sub, spec = r["seed"] % 10, r["spec"]
+        what = f"{profile} window seed {r['seed']} (sub-kind {sub}, start {spec.start_minute}, window {spec.peak_start}..{spec.peak_end}, T {r['T']})"
+        assert 150 <= r["T"] <= 400 and r["switching"], what
+        assert (r["changes"] == rw.WINDOW_CHANGES[sub]).all(), f"{what}: {r['changes']}"
+        assert not r["pk_quiet"], what
+        if sub == 0:
+            assert spec.peak_start == spec.peak_end and not r["pk_any"], what
+        if sub == 1:
+            assert (spec.peak_start, spec.peak_end) == (0, 1440) and r["pk_all"], what
+        if sub == 2:
+            assert spec.peak_end == 1440 and spec.start_minute + r["T"] > 1440, what
+        if sub == 3:
+            assert spec.peak_start > spec.peak_end and spec.start_minute + r["T"] > 1440 + spec.peak_end, what
+        if sub == 4:
+            assert spec.start_minute in (spec.peak_start, spec.peak_end), what
+            assert (r["pk0"] == int(in_window(spec, spec.start_minute))).all(), what
+            assert (r["pk0"] == int(spec.start_minute == spec.peak_start)).all(), what
+        if sub in (5, 6):
+            assert (spec.start_minute + r["T"] - (1 if sub == 5 else 0)) % 1440 in (spec.peak_start, spec.peak_end), what
+        if sub == 7:
+            assert spec.peak_start % 60 == 0 and spec.peak_end % 60 == 0, what
+        if sub == 8:
+            assert spec.peak_end == spec.peak_start + 1, what
+        if sub == 9:
+            assert 1440 <= spec.start_minute <= 1440 * 1001 and (spec.peak_end - spec.peak_start) % 1440 in (
+                *range(61, 121), *range(1320, 1380)), what
+    assert sum(r["spec"].peak_end == 1440 for r in rows) >= 4
+
+
+@pytest.mark.parametrize("profile", rw.TIMING_PROFILES)
+def test_short_worlds_hold_their_hour_boundary(profile):
+    rows = timing_rows(profile, "short")
+    assert [r["T"] for r in rows] == list(rw.SHORT_T)
+    for r in rows:
+        spec, T = r["spec"], r["T"]
+        assert spec.provision_delay_steps in (0, 1, T - 1, T, T + 1)
+        if T >= 2:
+            at = 1 if r["seed"] % 2 == 0 else T - 1
+            assert (spec.start_minute + at) % 60 == 0, (profile, r["seed"])
+    assert len({r["spec"].provision_delay_steps >= r["T"] for r in rows}) == 2  # both sides of delay = T
+
+
+@pytest.mark.parametrize("profile", rw.TIMING_PROFILES)
+def test_delay_worlds_never_ready_from_t_on(profile):
+    rows = timing_rows(profile, "delay")
+    assert len(rows) == 16
+    big = 0
+    for r in rows:
+        spec, T = r["spec"], r["T"]
+        assert 200 <= T <= 300
+        assert spec.provision_delay_steps == (5, 59, 60, 61, T - 1, T, T + 1, rw.MAX_DELAY)[r["seed"] % 8]
+        cas = [spec.reset_ca_s] + [x.consolidate_after_s for p in spec.pools for x in [p.base] + [p.profile[q] for q in range(3)]]
+        assert (max(cas) >= 3600) == (r["seed"] >= 8), (profile, r["seed"], cas)
+        big += max(cas) > 65535 * 60
+        if spec.provision_delay_steps >= T:
+            # no node ever becomes ready: no pod runs, none is ready at the end, pods wait, nothing is deleted
+            assert r["running"] == 0 and r["ready"] == 0 and r["pend_min"] > 0 and r["deletions"] == 0, (profile, r)
+    assert big == 2
+
+
+@pytest.mark.parametrize("profile", rw.TIMING_PROFILES)
+def test_window_and_delay_worlds_are_active(profile):
+    """The floors of the earlier profiles (launches in >= 70 %, deletions in
+    >= 60 % of the worlds) hold over each kind where the kind can reach them,
+    and over both kinds together. Of the delay kind's 16 worlds, six have a
+    delay >= T by construction (no node is ever ready, so none is deleted) and
+    two have delay = T - 1 (a node launched at t = 0 is ready for the last
+    step alone): no draw lifts the whole kind to 60 % deletions. Its floor is
+    therefore set over the eight worlds with a delay < T - 1 (5, 59, 60, 61
+    steps), and its launch floor over all sixteen."""
+    window, delay = timing_rows(profile, "window"), timing_rows(profile, "delay")
+    can = [r for r in delay if r["spec"].provision_delay_steps < r["T"] - 1]
+    assert len(can) == 8
+    got = {"launch": share(window + delay, "launch"), "delete": share(window + delay, "delete"),
+           "window launch": share(window, "launch"), "window delete": share(window, "delete"),
+           "delay launch": share(delay, "launch"), "delay delete, delay < T - 1": share(can, "delete")}
+    print(profile, got)
+    for k, v in got.items():
+        assert v >= (0.70 if "launch" in k else 0.60), got
+
+
+def test_max_and_pending_limit_worlds_are_at_the_limits():
+    for profile in rw.MAX_PROFILES:
+        spec = rw.draw(profile, 0, timing="max")[0]
+        assert (spec.n_steps, spec.start_minute) == (65535, rw.MAX_START) and rw.MAX_START + 65535 == 2**31 - 1
+    spec, sc, load = rw.pend_limit_world()
+    res, _ = po.rollout(spec, sc, load, threads=THREADS)
+    assert spec.provision_delay_steps == spec.n_steps == 65535 and spec.base_nodes == 0
+    assert (res["pending_pod_minutes"] == 2_147_385_345).all() and 32767 * 65535 == 2_147_385_345 == 2**31 - 98_303
+
+
+def test_consolidate_after_limit_world_tells_the_clamp():
+    """Empty nodes stand for 65470 steps: never deleted at 66667 steps of
+    consolidateAfter, deleted at 32767 (a kernel that clamped its copy at
+    0x7FFF would delete them at the first value too)."""
+    spec, sc, load = rw.ca_limit_world()
+    res, _ = po.rollout(spec, sc, load, threads=THREADS)
+    assert rw.CA_BEYOND_T > 65535 * 60 and (res["deletions"] == 0).all()
+    assert (res["final_nodes"] >= 2).sum() >= sc.n // 2, res["final_nodes"]
+    res, _ = po.rollout(*rw.ca_limit_world(32767 * 60), threads=THREADS)
+    assert (res["deletions"] > 0).sum() >= sc.n // 2, res["deletions"]
+
+
+def model_case(profile, kind, seed):
+    """spec_model against the oracle on a time-axis world's first three scenarios; False outside its scope."""
+    spec, sc, load = rw.draw(profile, seed, timing=kind)
+    if not in_model_scope(spec):
+        return False
+    try:
+        compare_model(spec, sc.slice(0, 3), np.ascontiguousarray(load[:, :, :3]))
+    except AssertionError as e:
+        raise AssertionError(f"{profile} {kind} seed {seed}: {e}") from None
+    return True
+
+
+@pytest.mark.parametrize("kind", ["window", "short"])
+@pytest.mark.parametrize("profile", rw.TIMING_PROFILES)
+def test_time_axis_spec_model_equals_oracle(profile, kind):
+    ran = sum(model_case(profile, kind, seed) for seed in rw.timing_seeds(profile, kind))
+    assert ran >= 1, f"{profile} {kind}: no world inside spec_model's scope"
+
+
+@pytest.mark.parametrize("profile,seed", [(p, s) for p in rw.TIMING_PROFILES for s in rw.DAYS_SEEDS[p]])
+def test_days_spec_model_equals_oracle(profile, seed):
+    """Every days world inside spec_model's scope, one case per world (the
+    Python model needs 0.4-8 s for a world, 13-34 s for a d1_sync15 one: four
+    decisions per step). A world outside the scope (multi-node consolidation,
+    extra KEDA triggers) has nothing to compare; the case below holds the count."""
+    model_case(profile, "days", seed)
+
+
+def test_days_spec_model_covers_every_profile():
+    """56 of the 68 days worlds are inside the model's scope, at least one of every profile."""
+    n = {p: sum(in_model_scope(rw.draw(p, s, timing="days")[0]) for s in rw.DAYS_SEEDS[p]) for p in rw.TIMING_PROFILES}
+    assert min(n.values()) >= 1 and sum(n.values()) == 56, n
