@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 STEP_SECONDS = 60
 MAX_TYPES = 1024
 MAX_ZONES = 4
@@ -163,6 +163,46 @@ def sweep_stat(cost=("sum",), slo=("sum",), gco2=("sum",), energy=("sum",)) -> S
     return st
 
 
+TL_NONE, TL_REPLICAS, TL_PENDING, TL_NODES = 0, 1, 2, 3
+TL_FIELDS = {"none": TL_NONE, "replicas": TL_REPLICAS, "pending": TL_PENDING, "nodes": TL_NODES}
+
+
+class TimelineSpec(C.Structure):
+    """ccka_timeline_spec: grid size, bucket width in steps, and the field whose
+    nearest-rank quantile every row also carries (docs/SEMANTICS.md 7)."""
+    _fields_ = [("grid_size", C.c_int64), ("step_bucket", C.c_int32), ("q_field", C.c_int32),
+                ("q_ppm", C.c_int32), ("_pad", C.c_int32)]
+
+
+class TimelineRow(C.Structure):
+    """ccka_timeline_row: one (grid, step bucket) of the fleet timeline."""
+    _fields_ = [("grid", C.c_int64), ("t0", C.c_int64), ("samples", C.c_int64),
+                ("sum_replicas", C.c_int64), ("sum_pending", C.c_int64), ("sum_nodes_spot", C.c_int64),
+                ("sum_nodes_od", C.c_int64), ("flag_count", C.c_int64 * 8),
+                ("max_replicas", C.c_int32), ("max_pending", C.c_int32), ("max_nodes", C.c_int32),
+                ("min_nodes", C.c_int32), ("q_value", C.c_int64)]
+
+
+def timeline_spec(grid_size, step_bucket=1, q_field=TL_NONE, q_ppm=0) -> TimelineSpec:
+    """TimelineSpec; q_field a TL_* value or "none" / "replicas" / "pending" / "nodes"."""
+    f = TL_FIELDS[q_field] if isinstance(q_field, str) else int(q_field)
+    return TimelineSpec(int(grid_size), int(step_bucket), f, int(q_ppm), 0)
+
+
+def timeline_dtype():
+    """numpy structured dtype laid out exactly as ccka_timeline_row."""
+    import numpy as np
+    fields = []
+    for name, ct in TimelineRow._fields_:
+        if hasattr(ct, "_length_"):
+            fields.append((name, "<i8", (ct._length_,)))
+        else:
+            fields.append((name, "<i8" if ct is C.c_int64 else "<i4"))
+    dt = np.dtype(fields)
+    assert dt.itemsize == C.sizeof(TimelineRow)
+    return dt
+
+
 class Detail(C.Structure):
     """ccka_detail: per-pool / base-group / per-deployment breakdown (ccka_set_detail)."""
     _fields_ = [("pool_cost_uphmin", C.c_int64 * MAX_POOLS), ("pool_energy_nwmin", C.c_int64 * MAX_POOLS),
@@ -198,7 +238,7 @@ class TraceGen(C.Structure):
 
 
 STRUCT_ORDER = [ItType, Pool, Deployment, World, Scenarios, Results, TrajRec, Totals, TraceGen,
-                GridStats, Detail, SweepStat]
+                GridStats, Detail, SweepStat, TimelineSpec, TimelineRow]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ENGINE_LIB = os.path.join(os.path.dirname(PKG_DIR), "csrc", "build", "libccka.so")
@@ -272,6 +312,8 @@ def load_engine(path: str | None = None):
         "ccka_get_grid_stat": (C.c_int, [vp, C.c_int64, C.POINTER(SweepStat), C.POINTER(GridStats), C.c_int64]),
         "ccka_pareto_frontier_stat": (C.c_int, [vp, C.c_int64, C.POINTER(SweepStat), C.POINTER(GridStats),
                                                 C.c_int32, C.POINTER(C.c_int32)]),
+        "ccka_timeline_rows": (C.c_int64, [C.c_int64, C.c_int32, C.POINTER(TimelineSpec)]),
+        "ccka_get_timeline": (C.c_int, [vp, C.POINTER(TimelineSpec), C.c_void_p, C.c_int64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -293,6 +335,7 @@ EXPORTED = [
     "ccka_policy_rollout", "ccka_get_policy_actions", "ccka_trajectory_layout", "ccka_get_trajectory_native",
     "ccka_policy_grad", "ccka_get_policy_samples", "ccka_mlp_backward", "ccka_totals_pack", "ccka_totals_finish",
     "ccka_sweep_rank", "ccka_get_grid_stat", "ccka_pareto_frontier_stat",
+    "ccka_timeline_rows", "ccka_get_timeline",
 ]
 TOTALS_INT64, TOTALS_BLOCK = 10, 11  # CCKA_TOTALS_INT64, CCKA_TOTALS_BLOCK
 EOVERFLOW = -8

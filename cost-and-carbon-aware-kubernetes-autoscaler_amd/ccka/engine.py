@@ -231,6 +231,37 @@ class Engine:
                   "ccka_debug_grid_stat")
         return _grid_array(out, ng)
 
+    # ---- fleet timeline (docs/SEMANTICS.md 7) ----
+    def timeline(self, grid_size: int, step_bucket: int = 1, q_field=0, q_ppm: int = 0) -> np.ndarray:
+        """The last rollout's trajectory records reduced on the device per grid
+        and bucket of step_bucket steps (ccka_get_timeline): a structured array
+        (abi.timeline_dtype()) shaped (n_grids, n_buckets). q_field (abi.TL_* or
+        its name) adds that field's nearest-rank quantile at q_ppm as q_value."""
+        spec = abi.timeline_spec(grid_size, step_bucket, q_field, q_ppm)
+        rows = self.lib.ccka_timeline_rows(self.n, self.T, C.byref(spec))
+        out = np.zeros(max(rows, 1), abi.timeline_dtype())
+        # rows < 0: the call names the rule that fails (or the missing trajectory)
+        self._chk(self.lib.ccka_get_timeline(self.ctx, C.byref(spec), out.ctypes.data, max(rows, 0)),
+                  "ccka_get_timeline")
+        return out[:rows].reshape(self.n // grid_size, -1)
+
+    def debug_timeline(self, recs, layout: int, grid_size: int, step_bucket: int = 1, q_field=0,
+                       q_ppm: int = 0) -> np.ndarray:
+        """Internal: timeline's kernel path on given records (TRAJ_DTYPE), shaped
+        (T, N) for abi.TRAJ_TN or (N, T) for abi.TRAJ_NT; grid ids from 0."""
+        a = np.ascontiguousarray(recs, TRAJ_DTYPE)
+        assert a.ndim == 2 and layout in (abi.TRAJ_TN, abi.TRAJ_NT)
+        n, steps = a.shape if layout == abi.TRAJ_NT else a.shape[::-1]
+        spec = abi.timeline_spec(grid_size, step_bucket, q_field, q_ppm)
+        rows = self.lib.ccka_timeline_rows(n, steps, C.byref(spec))
+        out = np.zeros(max(rows, 1), abi.timeline_dtype())
+        fn = self.lib.ccka_debug_timeline
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(abi.TimelineSpec),
+                       C.c_void_p]
+        self._chk(fn(self.ctx, a.ctypes.data, n, steps, layout, C.byref(spec), out.ctypes.data),
+                  "ccka_debug_timeline")
+        return out[:rows].reshape(n // grid_size, -1)
+
     TOTALS_COLUMNS = (("cost_uphmin", np.int64), ("slo_minutes", np.int32), ("pending_pod_minutes", np.int64),
                       ("node_min_spot", np.int32), ("node_min_od", np.int32), ("launches", np.int32),
                       ("deletions", np.int32), ("energy_wmin", np.float64), ("gco2", np.float64))

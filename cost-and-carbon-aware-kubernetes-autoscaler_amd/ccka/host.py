@@ -42,6 +42,9 @@ def lib():
                                            C.c_int64, C.POINTER(abi.Results), C.c_int64, C.c_int64,
                                            C.c_int64, C.c_int64, C.c_char_p, C.c_int64,
                                            C.POINTER(C.c_int64)]),
+            "ccka_host_export_timeline": (C.c_int, [vp, C.c_int32, C.POINTER(abi.World),
+                                                    C.POINTER(abi.TimelineSpec), C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
             "ccka_host_set_admission": (C.c_int, [vp, C.c_uint32]),
             "ccka_host_admission_review": (C.c_int, [vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int64]),
         }
@@ -57,7 +60,7 @@ HOST_EXPORTED = ["ccka_host_open", "ccka_host_close", "ccka_host_last_error", "c
                  "ccka_host_patch", "ccka_host_get_json", "ccka_host_policy_patch",
                  "ccka_host_burst_manifest", "ccka_host_build_world", "ccka_host_summary",
                  "ccka_host_export", "ccka_host_set_admission", "ccka_host_admission_review",
-                 "ccka_host_label", "ccka_host_export_detail"]
+                 "ccka_host_label", "ccka_host_export_detail", "ccka_host_export_timeline"]
 
 # Kyverno guard policies (04_kyverno.sh:24-75), ccka_host.h CCKA_ADMIT_*
 ADMIT_REQUIRE_REQUESTS_LIMITS = 1
@@ -161,6 +164,20 @@ class Host:
         if self.L.ccka_host_export_detail(*args, buf, need.value, C.byref(need)) != 0:
             self._err("export_detail")
         return buf.value.decode()
+
+    def export_timeline(self, world, spec, rows, fmt=EXPORT_PROMETHEUS, start_unix_ms=0) -> str:
+        """Fleet timeline export (ccka_host_export_timeline): Prometheus text or CSV of
+        `rows` (Engine.timeline's array, any shape) under `spec` (abi.timeline_spec)."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, abi.timeline_dtype()).ravel()
+        need = C.c_int64(0)
+        args = (self.h, fmt, C.byref(world), C.byref(spec), rows.ctypes.data, rows.size, start_unix_ms)
+        if self.L.ccka_host_export_timeline(*args, None, 0, C.byref(need)) != 0 and need.value <= 0:
+            self._err("export_timeline")
+        buf = C.create_string_buffer(need.value)
+        if self.L.ccka_host_export_timeline(*args, buf, need.value, C.byref(need)) != 0:
+            self._err("export_timeline")
+        return buf.raw[:need.value - 1].decode()
 
     def export(self, world, results: dict, traj, fmt=EXPORT_PROMETHEUS, s0=0, n=None, first_id=0,
                start_unix_ms=0) -> str:

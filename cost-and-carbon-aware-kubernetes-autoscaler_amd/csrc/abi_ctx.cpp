@@ -366,7 +366,8 @@ int32_t ccka_struct_sizes(int64_t* out, int32_t n) {
   const int64_t s[] = {sizeof(ccka_itype),    sizeof(ccka_pool),    sizeof(ccka_deployment),
                        sizeof(ccka_world),    sizeof(ccka_scenarios), sizeof(ccka_results),
                        sizeof(ccka_traj_rec), sizeof(ccka_totals),  sizeof(ccka_trace_gen),
-                       sizeof(ccka_grid_stats), sizeof(ccka_detail), sizeof(ccka_sweep_stat)};
+                       sizeof(ccka_grid_stats), sizeof(ccka_detail), sizeof(ccka_sweep_stat),
+                       sizeof(ccka_timeline_spec), sizeof(ccka_timeline_row)};
   const int32_t m = (int32_t)(sizeof s / sizeof s[0]);
   int32_t k = 0;
   for (; k < m && k < n; ++k) out[k] = s[k];

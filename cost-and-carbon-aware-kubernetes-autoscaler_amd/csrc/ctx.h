@@ -121,6 +121,8 @@ struct ccka_ctx {
   Buf<int32_t> d_gn;
   Buf<uint8_t> d_gflags;
   Buf<ccka_grid_stats> d_gfront;   // the frontier (local or global)
+  // fleet timeline (SEMANTICS 7): the rows of the last ccka_get_timeline
+  Buf<ccka_timeline_row> d_tlrows;
   // learned MLP policy (config 5)
   bool mlp_have_w = false;
   Buf<ccka::mlp_bf16x8> d_w1f;

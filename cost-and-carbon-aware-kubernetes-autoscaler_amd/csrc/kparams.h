@@ -417,4 +417,22 @@ hipError_t launch_pg_fill(uint16_t* x, int64_t n, int64_t valid, uint16_t v, hip
 hipError_t launch_traj_transpose(const ccka_traj_rec* in, ccka_traj_rec* out, int64_t N, int64_t T, int64_t t0,
                                  int64_t tc, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// Fleet timeline (timeline.hip, SEMANTICS 7): the trajectory records reduced
+// per (grid, step bucket); rows[n_grids * n_buckets], grid-major
+// ---------------------------------------------------------------------------
+struct TimelineParams {
+  const ccka_traj_rec* recs;  // [N][T] (nt != 0) or [T][N]
+  ccka_timeline_row* rows;
+  int64_t N, G;               // scenarios, grid size (N = n_grids * G)
+  int64_t n_grids, first_grid;
+  int32_t T, B;               // steps, bucket width
+  int32_t n_buckets, nt;
+  int32_t q_field, q_ppm;     // CCKA_TL_*; quantile in ppm
+};
+// every row re-initialised (ids, counts, neutral sums and extrema), then the sums
+hipError_t launch_timeline_sum(const TimelineParams& p, int cus, hipStream_t s);
+// q_value of every row (q_field != NONE; NODES reads the extrema the sums left)
+hipError_t launch_timeline_select(const TimelineParams& p, int cus, hipStream_t s);
+
 }  // namespace ccka

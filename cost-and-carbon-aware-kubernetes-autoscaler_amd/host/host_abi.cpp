@@ -526,4 +526,88 @@ int ccka_host_export_detail(ccka_host* h, const ccka_world* w, const ccka_detail
   });
 }
 
+int ccka_host_export_timeline(ccka_host* h, int32_t format, const ccka_world* w, const ccka_timeline_spec* spec,
+                              const ccka_timeline_row* rows, int64_t n_rows, int64_t start_unix_ms, char* out,
+                              int64_t cap, int64_t* needed) {
+  return guarded(h, [&] {
+    if (needed) *needed = 0;
+    if (!w || !spec || n_rows < 0 || (n_rows > 0 && !rows) || spec->q_field < CCKA_TL_NONE ||
+        spec->q_field > CCKA_TL_NODES || (format != CCKA_EXPORT_PROMETHEUS && format != CCKA_EXPORT_CSV))
+      return (int)CCKA_EINVAL;
+    const int start = ((w->start_minute % 1440) + 1440) % 1440;
+    std::string o;
+    if (format == CCKA_EXPORT_CSV) {
+      o.reserve((size_t)(n_rows * 120 + 256));
+      o += "grid,t0,minute,samples,sum_replicas,sum_pending,sum_nodes_spot,sum_nodes_od,max_replicas,max_pending,"
+           "max_nodes,min_nodes,count_bit0,count_bit1,count_bit2,count_bit3,count_bit4,count_bit5,count_bit6,"
+           "count_bit7,q_value\n";
+      for (int64_t i = 0; i < n_rows; ++i) {
+        const ccka_timeline_row& x = rows[i];
+        appendf(o, "%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%d,%d,%d,%d", (long long)x.grid, (long long)x.t0,
+                (long long)((start + x.t0) % 1440), (long long)x.samples, (long long)x.sum_replicas,
+                (long long)x.sum_pending, (long long)x.sum_nodes_spot, (long long)x.sum_nodes_od, x.max_replicas,
+                x.max_pending, x.max_nodes, x.min_nodes);
+        for (int b = 0; b < 8; ++b) appendf(o, ",%lld", (long long)x.flag_count[b]);
+        appendf(o, ",%lld\n", (long long)x.q_value);
+      }
+    } else {
+      o.reserve((size_t)(n_rows * 18 * 80 + 4096));
+      auto ts = [&](const ccka_timeline_row& x) {
+        return (long long)(start_unix_ms + x.t0 * CCKA_STEP_SECONDS * 1000);
+      };
+      // one family: `extra` = further labels (with their leading comma)
+      auto series = [&](const char* name, const char* help, const char* extra, auto value, bool declare = true) {
+        if (declare) appendf(o, "# HELP %s %s\n# TYPE %s gauge\n", name, help, name);
+        for (int64_t i = 0; i < n_rows; ++i) {
+          appendf(o, "%s{grid=\"%lld\"%s} %lld %lld\n", name, (long long)rows[i].grid, extra,
+                  (long long)value(rows[i]), ts(rows[i]));
+        }
+      };
+      using Row = ccka_timeline_row;
+      series("ccka_fleet_samples", "Trajectory samples of the grid in the step bucket (scenarios x steps).", "",
+             [](const Row& x) { return x.samples; });
+      series("ccka_fleet_replicas_sum", "Desired pods summed over the samples.", "",
+             [](const Row& x) { return x.sum_replicas; });
+      series("ccka_fleet_pending_sum", "Pending pods summed over the samples.", "",
+             [](const Row& x) { return x.sum_pending; });
+      series("ccka_fleet_nodes_sum", "Karpenter nodes summed over the samples, by capacity type.",
+             ",capacity_type=\"spot\"", [](const Row& x) { return x.sum_nodes_spot; });
+      series("ccka_fleet_nodes_sum", "", ",capacity_type=\"on-demand\"", [](const Row& x) { return x.sum_nodes_od; },
+             false);
+      series("ccka_fleet_replicas_max", "Largest desired pod count of a sample.", "",
+             [](const Row& x) { return (int64_t)x.max_replicas; });
+      series("ccka_fleet_pending_max", "Largest pending pod count of a sample.", "",
+             [](const Row& x) { return (int64_t)x.max_pending; });
+      series("ccka_fleet_nodes_max", "Largest Karpenter node count of a sample (both capacity types).", "",
+             [](const Row& x) { return (int64_t)x.max_nodes; });
+      series("ccka_fleet_nodes_min", "Smallest Karpenter node count of a sample (both capacity types).", "",
+             [](const Row& x) { return (int64_t)x.min_nodes; });
+      static const char* ev[6] = {"launch", "deletion", "slo_violation", "drift_deletion", "replacement_launch",
+                                  "multi_consolidation"};
+      for (int e = 0; e < 6; ++e) {
+        const std::string lab = std::string(",event=\"") + ev[e] + "\"";
+        series("ccka_fleet_step_events", "Samples whose step launched or deleted a node, violated the SLO, ...",
+               lab.c_str(), [e](const Row& x) { return x.flag_count[e + 1]; }, e == 0);
+      }
+      series("ccka_fleet_policy_peak_samples", "Samples under the peak NodePool profile.", "",
+             [](const Row& x) { return x.flag_count[0]; });
+      if (spec->q_field != CCKA_TL_NONE) {
+        static const char* fld[4] = {"", "replicas", "pending", "nodes"};
+        const std::string lab =
+            std::string(",field=\"") + fld[spec->q_field] + "\",q_ppm=\"" + std::to_string(spec->q_ppm) + "\"";
+        series("ccka_fleet_quantile", "Nearest-rank quantile of the field over the samples.", lab.c_str(),
+               [](const Row& x) { return x.q_value; });
+      }
+    }
+    if (needed) *needed = (int64_t)o.size() + 1;
+    if (!out || (int64_t)o.size() + 1 > cap) {
+      h->err = "output buffer too small: need " + std::to_string(o.size() + 1);
+      return (int)CCKA_EINVAL;
+    }
+    std::memcpy(out, o.data(), o.size());
+    out[o.size()] = 0;
+    return (int)CCKA_OK;
+  });
+}
+
 }  // extern "C"

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CCKA_ABI_VERSION 6
+#define CCKA_ABI_VERSION 7
 
 #define CCKA_STEP_SECONDS 60
 #define CCKA_MAX_TYPES 1024
@@ -333,6 +333,37 @@ typedef struct ccka_sweep_stat {
   int32_t q_ppm[4];
 } ccka_sweep_stat;
 
+/* Fleet timeline (docs/SEMANTICS.md §7): the last rollout's trajectory records
+ * reduced on the device per (grid, step bucket). Grids as in the sweep (grid g =
+ * global ids [g*grid_size, (g+1)*grid_size), the batch holds whole grids);
+ * bucket b covers steps [b*step_bucket, min((b+1)*step_bucket, T)), so there
+ * are ceil(T / step_bucket) buckets. q_field chooses one field whose
+ * nearest-rank quantile (q_ppm as in ccka_sweep_stat) each row also carries.
+ * Integers only: every value is exact and independent of the reduction order.
+ * grid_size * min(step_bucket, T) <= 2^31 is required. 24 bytes. */
+enum { CCKA_TL_NONE = 0, CCKA_TL_REPLICAS = 1, CCKA_TL_PENDING = 2, CCKA_TL_NODES = 3 };
+typedef struct ccka_timeline_spec {
+  int64_t grid_size;
+  int32_t step_bucket;
+  int32_t q_field;  /* CCKA_TL_*; NODES = nodes_spot + nodes_od */
+  int32_t q_ppm;    /* 0 .. 1000000; ignored for CCKA_TL_NONE */
+  int32_t _pad;
+} ccka_timeline_spec;
+/* One row per (grid, bucket), grid-major: row = local grid * n_buckets + bucket.
+ * Its samples are the records of the grid's scenarios at the bucket's steps.
+ * 144 bytes. */
+typedef struct ccka_timeline_row {
+  int64_t grid;     /* global grid id */
+  int64_t t0;       /* the bucket's first step */
+  int64_t samples;  /* grid_size * steps in the bucket */
+  int64_t sum_replicas, sum_pending, sum_nodes_spot, sum_nodes_od;
+  int64_t flag_count[8];  /* samples with bit 0..7 of flags set (bits 8..15 are ignored) */
+  int32_t max_replicas, max_pending;
+  int32_t max_nodes, min_nodes;  /* over nodes_spot + nodes_od (up to 131070) */
+  int64_t q_value;  /* x(k) of q_field over the samples, k = ccka_sweep_rank(samples, q_ppm),
+                     * values ordered as signed int32; 0 for CCKA_TL_NONE */
+} ccka_timeline_row;
+
 /* Synthetic load-trace generator (docs/SEMANTICS.md §4). ccka_gen_load accepts
  * the parameters with which every intermediate of §4 stays inside the
  * arithmetic that evaluates it, for every scenario, step and draw, and
@@ -365,7 +396,8 @@ typedef struct ccka_ctx ccka_ctx;
 int32_t ccka_abi_version(void);
 /* sizes of the ABI structs, for binding self-checks: fills out[0..n) in the
  * order itype, pool, deployment, world, scenarios, results, traj_rec, totals,
- * trace_gen, grid_stats, detail, sweep_stat; returns the count written. */
+ * trace_gen, grid_stats, detail, sweep_stat, timeline_spec, timeline_row;
+ * returns the count written. */
 int32_t ccka_struct_sizes(int64_t* out, int32_t n);
 int ccka_open(ccka_ctx** out, int device_ordinal);
 void ccka_close(ccka_ctx* ctx);
@@ -454,6 +486,20 @@ int ccka_get_grid_stat(ccka_ctx* ctx, int64_t grid_size, const ccka_sweep_stat* 
  * statistic crosses GPUs. */
 int ccka_pareto_frontier_stat(ccka_ctx* ctx, int64_t grid_size, const ccka_sweep_stat* stat, ccka_grid_stats* out,
                               int32_t capacity, int32_t* n_out);
+
+/* ---- fleet timeline (docs/SEMANTICS.md §7) ---------------------------- */
+/* rows of a timeline of n scenarios x n_steps under spec; -1 where the call would be CCKA_EINVAL. No context. */
+int64_t ccka_timeline_rows(int64_t n, int32_t n_steps, const ccka_timeline_spec* spec);
+/* The timeline of the last rollout's trajectory records, reduced on the device
+ * in whichever layout the engine wrote (after ccka_rollout, ccka_policy_rollout
+ * and ccka_policy_grad alike); the records stay untouched. out[n_rows], n_rows =
+ * ccka_timeline_rows(n, n_steps, spec). CCKA_ESTATE before any rollout or when
+ * the last one had no trajectory (as ccka_get_trajectory). CCKA_EINVAL for a
+ * null spec, a batch that does not hold whole grids (first_id and n multiples of
+ * grid_size), step_bucket < 1, q_field outside 0..3, a non-NONE q_ppm outside
+ * [0, 1000000], grid_size * min(step_bucket, n_steps) > 2^31, more than 2^24
+ * rows, or another n_rows. */
+int ccka_get_timeline(ccka_ctx* ctx, const ccka_timeline_spec* spec, ccka_timeline_row* out, int64_t n_rows);
 
 /* ---- learned MLP control policy (BASELINE config 5) ------------------- */
 /* Weights of the state(64) -> 256 -> 256 -> actions(8) ReLU policy: bf16 bit

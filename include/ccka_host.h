@@ -115,6 +115,27 @@ int ccka_host_export(ccka_host* h, int32_t format, const ccka_world* w, const cc
  * kube_deployment_status_replicas_ready. Buffer rules as ccka_host_export. */
 int ccka_host_export_detail(ccka_host* h, const ccka_world* w, const ccka_detail* detail, int64_t n,
                             int64_t first_id, int64_t start_unix_ms, char* out, int64_t cap, int64_t* needed);
+/* Fleet timeline export: rows[0..n_rows) of ccka_get_timeline under `spec`
+ * (the band panels of the demo_40_watch_* dashboards: the fleet over the day
+ * instead of one scenario). Integers only, in the _sum / _count convention,
+ * so the consumer divides by ccka_fleet_samples for a mean.
+ *   CCKA_EXPORT_PROMETHEUS: one sample per row at start_unix_ms + 60000 t0:
+ *     ccka_fleet_samples, ccka_fleet_replicas_sum, ccka_fleet_pending_sum,
+ *     ccka_fleet_nodes_sum{capacity_type}, ccka_fleet_replicas_max,
+ *     ccka_fleet_pending_max, ccka_fleet_nodes_max, ccka_fleet_nodes_min,
+ *     ccka_fleet_step_events{event} (flag bits 1..6: launch, deletion,
+ *     slo_violation, drift_deletion, replacement_launch,
+ *     multi_consolidation), ccka_fleet_policy_peak_samples (bit 0), each
+ *     labelled grid; with a quantile in the spec also
+ *     ccka_fleet_quantile{grid,field,q_ppm}.
+ *   CCKA_EXPORT_CSV: grid,t0,minute,samples,sum_replicas,sum_pending,
+ *     sum_nodes_spot,sum_nodes_od,max_replicas,max_pending,max_nodes,
+ *     min_nodes,count_bit0..count_bit7,q_value; minute = (start_minute + t0)
+ *     mod 1440.
+ * Buffer rules as ccka_host_export. */
+int ccka_host_export_timeline(ccka_host* h, int32_t format, const ccka_world* w, const ccka_timeline_spec* spec,
+                              const ccka_timeline_row* rows, int64_t n_rows, int64_t start_unix_ms, char* out,
+                              int64_t cap, int64_t* needed);
 
 #ifdef __cplusplus
 }
