@@ -118,10 +118,11 @@ def rollout_world(world, scen, load, traj=False, threads=1, detail=False, spec=N
     return (arrays, tr, det) if detail else (arrays, tr)
 
 
-def rollout_policy(spec, scen, load, act_target, act_cw, traj=False, threads=1, features=False):
+def rollout_policy(spec, scen, load, act_target, act_cw, traj=False, threads=1, features=False, detail=False):
     """Replay a closed-loop policy run (SEMANTICS 5): act_target / act_cw are the
     per-step actions [T][N]. Returns (results, trajectory or None, features
-    [T + 1][N][64] uint16 bf16 bits or None)."""
+    [T + 1][N][64] uint16 bf16 bits or None), plus the ccka_detail records of
+    the replay as a fourth element when detail=True."""
     w = spec.to_c()
     s = scen.to_c()
     load = np.ascontiguousarray(load, np.int32)
@@ -131,13 +132,14 @@ def rollout_policy(spec, scen, load, act_target, act_cw, traj=False, threads=1, 
     arrays, r = alloc_results(scen.n)
     tr = np.zeros((spec.n_steps, scen.n), TRAJ_DTYPE) if traj else None
     ft = np.zeros((spec.n_steps + 1, scen.n, 64), np.uint16) if features else None
+    det = np.zeros(scen.n, abi.detail_dtype()) if detail else None
     rc = lib().ccka_oracle_rollout_policy(C.byref(w), C.byref(s), load.ctypes.data_as(C.POINTER(C.c_int32)),
                                           C.byref(r), tr.ctypes.data_as(C.POINTER(abi.TrajRec)) if traj else None,
-                                          None, at.ctypes.data, ac.ctypes.data,
+                                          det.ctypes.data if detail else None, at.ctypes.data, ac.ctypes.data,
                                           ft.ctypes.data if features else None, threads)
     if rc != 0:
         raise abi.CckaError(f"oracle policy rollout failed: {rc}")
-    return arrays, tr, ft
+    return (arrays, tr, ft, det) if detail else (arrays, tr, ft)
 
 
 def policy_uniform(seed, gids, t):

@@ -33,6 +33,11 @@ the last value ccka_set_world accepts, consolidateAfter beyond the horizon
 (_timing_kind, _timing_post). They draw from a stream of their own, so the
 worlds of draw(profile, seed) are what they were before the kinds existed
 (world_digest; tests/test_random_worlds.py freezes a few).
+
+The closed-loop suite (tests/test_gpu_loop_worlds.py) reuses draw() and adds
+named worlds on streams of their own: loop_layout_world (12 and 16 deployment
+columns) and loop_lds_world (the two catalogs on either side of the fused
+loop's LDS rule).
 """
 from __future__ import annotations
 
@@ -875,3 +880,73 @@ def boundary_world(which: str):
     sc = _scenarios(rng, R, (0, 60, 300))
     sc.target_util_pct = None
     return spec, sc, _load(rng, spec.n_steps, [9000, 9000])
+
+
+def loop_layout_world(n_deploy: int):
+    """The closed-loop worlds of the two widest register layouts (kernel_dims:
+    12 and 16 deployment columns on 16 slots): n_deploy in (12, 16) columns
+    mixing HPA, static and KEDA deployments, one KEDA ScaledObject with two
+    triggers among them, 3 pools with limits, 130 scenarios, 90-120 steps with
+    an hour boundary and one edge of the peak window inside."""
+    assert n_deploy in (12, 16), n_deploy
+    rng = np.random.default_rng([20251205, 96, n_deploy])
+    cat, R, Z = _geo(rng)
+    on = int(rng.integers(0, 8))
+    disrupt = on != 0
+    cap_set = (2, 3) if disrupt else (1, 2, 3)
+    groups = [["hpa"], ["keda", "trigger"], ["static"]]
+    while sum(len(g) for g in groups) < n_deploy:
+        groups.append([pick(rng, ["hpa", "hpa", "static", "keda"])])
+    deploys, his = [], []
+    for j in rng.permutation(len(groups)):
+        hi = pick(rng, [3000, 9000])
+        for k in groups[j]:
+            if k == "hpa":
+                deploys.append(_hpa(rng, rules=pick(rng, ["default", "ring"]), tol_set=(0.1, 0.0, 0.25), cap_set=cap_set,
+                                    big=disrupt))
+            elif k == "static":
+                deploys.append(_static(rng))
+            elif k == "keda":
+                deploys.append(_keda(rng, hi, cap_set))
+            else:
+                deploys.append(keda_trigger(pick(rng, [300, 700, 2000]), pick(rng, [0, 200, hi // 8 + hi // 20])))
+            his.append(hi)
+    assert len(deploys) == n_deploy
+    pools = _pools(rng, Z, 3, disrupt=disrupt, limits=True)
+    spec = _world(rng, deploys, pools, cat, R, Z, 16, drift=on & 1, replace=(on >> 1) & 1, multi=(on >> 2) & 1)
+    T = int(rng.integers(90, 121))  # >= 60: a clock hour inside
+    start = int(rng.integers(0, 1440))
+    edge, other = (start + int(rng.integers(20, T - 19))) % 1440, _outside(rng, start, T)
+    spec.n_steps, spec.start_minute = T, start
+    spec.peak_start, spec.peak_end = (edge, other) if rng.integers(2) else (other, edge)
+    sc = _scenarios(rng, R, (0, 60, 300, 480), (2, 3, 3) if disrupt else (1, 2, 3), switch_p=0.95 if disrupt else 0.85)
+    return spec, sc, _load(rng, T, his)
+
+
+def loop_lds_world(fits: bool):
+    """The two worlds on either side of the fused closed loop's LDS rule
+    (abi_policy.cpp policy_loop: the general kernel's LDS, rounded up to 16,
+    plus the MLP's 149,632 B within 160 KiB): one HPA deployment on 8 slots,
+    two zones, two regions in the one block of 130 scenarios (span 2), and a
+    catalog of K types (fits) or K + 1, K the largest count for which the
+    restated rule (loop_check.fuses) admits the fused loop. The K-type world
+    is the other one without catalog entry (K + 1) // 2: same stream, same
+    prices, scenarios and load."""
+    from loop_check import fuses
+    R = Z = 2
+    K = max(k for k in range(1, abi.MAX_TYPES) if fuses(k, Z, R, 1, 8))
+    assert not fuses(K + 1, Z, R, 1, 8)
+    rng = np.random.default_rng([20251205, 95, 0])
+    cat = _catalog_wide(rng, K + 1, zero_cap=False)
+    hi = pick(rng, HIS)
+    dep = _hpa(rng, tol_set=(0.1, 0.0, 0.25))
+    spec = _world(rng, [dep], _pools(rng, Z, 2), cat, R, Z, 8)
+    sc = _scenarios(rng, R, (0, 60, 120, 300))
+    sc.region = (rng.permutation(N_SCEN) % R).astype(np.uint8)
+    load = _load(rng, spec.n_steps, [hi])
+    if fits:
+        keep = np.arange(K + 1) != (K + 1) // 2
+        spec.catalog = Catalog([n for n, k in zip(cat.names, keep) if k], cat.vcpu[keep], cat.mem_gib[keep],
+                               cat.max_pods[keep], cat.od_uph[keep])
+        spec.price = np.ascontiguousarray(spec.price[:, :, keep])
+    return spec, sc, load

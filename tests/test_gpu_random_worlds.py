@@ -33,9 +33,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import pyoracle as po
+import loop_check
 import random_worlds as rw
-from ccka import configs
 from parity import compare, oracle, run_engine
 
 pytestmark = pytest.mark.gpu
@@ -104,12 +103,6 @@ def _lpw(engine, v):
     assert fn(engine.ctx, v) == 0
 
 
-def _fused(engine, on):
-    fn = engine.lib.ccka_debug_policy_fused
-    fn.argtypes = [C.c_void_p, C.c_int32]
-    fn(engine.ctx, on)
-
-
 def _named(what, fn):
     try:
         return fn()
@@ -147,37 +140,10 @@ def check_world(engine, profile, seed, world=None, modes=None):
 
 
 def check_loop(engine, seed, launched, n=rw.N_SCEN, world=None):
-    spec, sc, load = world or rw.draw("loop", seed, n)
-    ws, bs = configs.mlp_weights(seed)
-    engine.set_world(spec)
-    engine.set_scenarios(sc)
-    engine.set_load(load)
-    engine.mlp_set_weights([configs.to_bf16_bits(w) for w in ws], bs)
-    runs = []
-    engine.debug_policy_features(True)
-    try:
-        for fused, want in ((1, 4), (0, 3)) if launched else ((1, 4),):
-            _fused(engine, fused)
-            engine.policy_rollout(trajectory=True, record=True)
-            got = engine.last_engine()[0]
-            assert got == want, f"profile loop seed {seed} fused {fused}: ran on engine {got}, expected {want}"
-            runs.append((engine.results(), engine.trajectory(), engine.policy_actions(),
-                         engine.debug_get_policy_features()))
-    finally:
-        _fused(engine, 1)
-        engine.debug_policy_features(False)
-    rg, tg, (at, ac), fg = runs[0]
-    rc, tc, fc = po.rollout_policy(spec, sc, load, at, ac, traj=True, threads=THREADS, features=True)
-    what = f"profile loop seed {seed} engine 4 (fused) vs oracle replay"
-    _named(what, lambda: compare(rg, rc, tg, tc))
-    bad = np.argwhere(fg != fc)
-    assert bad.size == 0, f"{what}: features differ at (t, i, f) {bad[:5].tolist()}"
-    if launched:
-        rl, tl, (atl, acl), fl = runs[1]
-        what = f"profile loop seed {seed} engine 3 (launched) vs engine 4 (fused)"
-        _named(what, lambda: compare(rl, rg, tl, tg))
-        assert np.array_equal(atl, at) and np.array_equal(acl, ac), f"{what}: actions differ"
-        assert np.array_equal(fl, fg), f"{what}: features differ"
+    """A loop-profile world on the fused loop (and the launched one) against the
+    oracle's replay of its recorded actions: tests/loop_check.py check_loop."""
+    loop_check.check_loop(engine, world or rw.draw("loop", seed, n), seed, f"profile loop seed {seed}",
+                          launched=launched, want=4)
 
 
 @pytest.mark.parametrize("chunk", range(CHUNKS))
