@@ -203,6 +203,49 @@ def timeline_dtype():
     return dt
 
 
+PAIRED_SAME = -1  # CCKA_PAIRED_SAME: each current grid against the snapshot's grid of the same id
+
+
+class PairedSpec(C.Structure):
+    """ccka_paired_spec: grid size, baseline grid of the snapshot (or PAIRED_SAME)
+    and the order statistic of the deltas per objective (docs/SEMANTICS.md 8)."""
+    _fields_ = [("grid_size", C.c_int64), ("base_grid", C.c_int64), ("stat", SweepStat)]
+
+
+class PairedObj(C.Structure):
+    """ccka_paired_obj: one objective's deltas of a current grid against its baseline."""
+    _fields_ = [("sum", C.c_int64), ("min", C.c_int64), ("max", C.c_int64), ("q_value", C.c_int64),
+                ("n_less", C.c_int64), ("n_greater", C.c_int64)]
+
+
+class PairedRow(C.Structure):
+    """ccka_paired_row: one current grid of the paired comparison."""
+    _fields_ = [("grid", C.c_int64), ("base", C.c_int64), ("pairs", C.c_int64), ("n_dominates", C.c_int64),
+                ("n_dominated", C.c_int64), ("obj", PairedObj * 4)]
+
+
+PAIRED_STRUCTS = [PairedSpec, PairedObj, PairedRow]  # the order of ccka_paired_sizes
+
+
+def paired_spec(grid_size, base_grid=PAIRED_SAME, stat=None) -> PairedSpec:
+    """PairedSpec; stat an abi.sweep_stat(...) (None: every objective SUM, no selection)."""
+    sp = PairedSpec(int(grid_size), int(base_grid), SweepStat())
+    if stat is not None:
+        sp.stat.kind[:] = list(stat.kind)
+        sp.stat.q_ppm[:] = list(stat.q_ppm)
+    return sp
+
+
+def paired_dtype():
+    """numpy structured dtype laid out exactly as ccka_paired_row: obj is a
+    sub-array of four records in STAT_OBJECTIVES order."""
+    import numpy as np
+    obj = np.dtype([(name, "<i8") for name, _ in PairedObj._fields_])
+    dt = np.dtype([(name, "<i8") for name, _ in PairedRow._fields_[:-1]] + [("obj", obj, (4,))])
+    assert dt.itemsize == C.sizeof(PairedRow)
+    return dt
+
+
 class Detail(C.Structure):
     """ccka_detail: per-pool / base-group / per-deployment breakdown (ccka_set_detail)."""
     _fields_ = [("pool_cost_uphmin", C.c_int64 * MAX_POOLS), ("pool_energy_nwmin", C.c_int64 * MAX_POOLS),
@@ -314,6 +357,11 @@ def load_engine(path: str | None = None):
                                                 C.c_int32, C.POINTER(C.c_int32)]),
         "ccka_timeline_rows": (C.c_int64, [C.c_int64, C.c_int32, C.POINTER(TimelineSpec)]),
         "ccka_get_timeline": (C.c_int, [vp, C.POINTER(TimelineSpec), C.c_void_p, C.c_int64]),
+        "ccka_paired_sizes": (C.c_int32, [C.POINTER(C.c_int64), C.c_int32]),
+        "ccka_paired_capture": (C.c_int, [vp, C.c_int64]),
+        "ccka_paired_export": (C.c_int, [vp, C.c_int64, C.c_void_p, C.c_int64]),
+        "ccka_paired_import": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+        "ccka_get_paired": (C.c_int, [vp, C.POINTER(PairedSpec), C.c_void_p, C.c_int64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -336,6 +384,7 @@ EXPORTED = [
     "ccka_policy_grad", "ccka_get_policy_samples", "ccka_mlp_backward", "ccka_totals_pack", "ccka_totals_finish",
     "ccka_sweep_rank", "ccka_get_grid_stat", "ccka_pareto_frontier_stat",
     "ccka_timeline_rows", "ccka_get_timeline",
+    "ccka_paired_sizes", "ccka_paired_capture", "ccka_paired_export", "ccka_paired_import", "ccka_get_paired",
 ]
 TOTALS_INT64, TOTALS_BLOCK = 10, 11  # CCKA_TOTALS_INT64, CCKA_TOTALS_BLOCK
 EOVERFLOW = -8
@@ -349,3 +398,8 @@ def check_sizes(lib) -> None:
     got = list(buf[:n])
     if got != want:
         raise CckaError(f"ABI struct size mismatch: lib {got} vs python {want}")
+    n = lib.ccka_paired_sizes(buf, 16)
+    want = [C.sizeof(s) for s in PAIRED_STRUCTS]
+    got = list(buf[:n])
+    if got != want:
+        raise CckaError(f"paired struct size mismatch: lib {got} vs python {want}")

@@ -262,6 +262,65 @@ class Engine:
                   "ccka_debug_timeline")
         return out[:rows].reshape(n // grid_size, -1)
 
+    # ---- paired comparison (docs/SEMANTICS.md 8) ----
+    def paired_capture(self, grid_size: int):
+        """Keep the last rollout's batch as the snapshot later paired() calls
+        compare against (ccka_paired_capture); it survives new worlds,
+        scenarios, traces and rollouts until the next capture or import."""
+        self._chk(self.lib.ccka_paired_capture(self.ctx, C.c_int64(grid_size)), "ccka_paired_capture")
+        self._paired_gs = grid_size
+
+    def paired(self, grid_size: int, base_grid: int = abi.PAIRED_SAME, stat: abi.SweepStat | None = None) -> np.ndarray:
+        """One row (abi.paired_dtype()) per grid of the last rollout: its
+        per-position deltas against grid base_grid of the snapshot, or with
+        abi.PAIRED_SAME against the snapshot's grid of the same id; stat
+        (abi.sweep_stat) adds a quantile or tail sum of the deltas per objective."""
+        spec = abi.paired_spec(grid_size, base_grid, stat)
+        ng = self.n // grid_size if grid_size > 0 else 0
+        out = np.zeros(max(ng, 1), abi.paired_dtype())
+        self._chk(self.lib.ccka_get_paired(self.ctx, C.byref(spec), out.ctypes.data, C.c_int64(ng)),
+                  "ccka_get_paired")
+        return out[:ng]
+
+    def paired_export(self, grid: int) -> np.ndarray:
+        """The snapshot's global grid `grid` as an int64 block [4][grid_size]
+        (cost, SLO minutes, gCO2 ug, energy uW.min); the size is the last
+        capture's or import's grid_size."""
+        gs = getattr(self, "_paired_gs", 0)
+        out = np.zeros((4, max(gs, 1)), np.int64)
+        self._chk(self.lib.ccka_paired_export(self.ctx, C.c_int64(grid), out.ctypes.data, C.c_int64(4 * gs)),
+                  "ccka_paired_export")
+        return out
+
+    def paired_import(self, grid_size: int, n_traces: int, grid: int, block: np.ndarray):
+        """A one-grid snapshot (global grid id `grid`) from a paired_export block."""
+        a = np.ascontiguousarray(block, np.int64)
+        self._chk(self.lib.ccka_paired_import(self.ctx, C.c_int64(grid_size), C.c_int64(n_traces), C.c_int64(grid),
+                                              a.ctypes.data, C.c_int64(a.size)), "ccka_paired_import")
+        self._paired_gs = grid_size
+
+    PAIRED_COLUMNS = (("cost_uphmin", np.int64), ("slo_minutes", np.int32), ("gco2", np.float64),
+                      ("energy_wmin", np.float64))
+
+    def debug_paired(self, cur, base, grid_size: int, base_grid: int = abi.PAIRED_SAME,
+                     stat: abi.SweepStat | None = None) -> np.ndarray:
+        """Internal: paired()'s two kernels on given result columns (mappings
+        with PAIRED_COLUMNS; whole grids of grid_size, grid ids from 0 on both
+        sides); the context's snapshot stays."""
+        a = [np.ascontiguousarray(cur[k], dt) for k, dt in self.PAIRED_COLUMNS]
+        b = [np.ascontiguousarray(base[k], dt) for k, dt in self.PAIRED_COLUMNS]
+        n, nb = len(a[0]), len(b[0])
+        assert all(x.shape == (n,) for x in a) and all(x.shape == (nb,) for x in b)
+        spec = abi.paired_spec(grid_size, base_grid, stat)
+        ng = n // max(1, grid_size)
+        out = np.zeros(max(ng, 1), abi.paired_dtype())
+        fn = self.lib.ccka_debug_paired
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_int64,
+                       C.POINTER(abi.PairedSpec), C.c_void_p]
+        self._chk(fn(self.ctx, *[x.ctypes.data for x in a], n, *[x.ctypes.data for x in b], nb, C.byref(spec),
+                     out.ctypes.data), "ccka_debug_paired")
+        return out[:ng]
+
     TOTALS_COLUMNS = (("cost_uphmin", np.int64), ("slo_minutes", np.int32), ("pending_pod_minutes", np.int64),
                       ("node_min_spot", np.int32), ("node_min_od", np.int32), ("launches", np.int32),
                       ("deletions", np.int32), ("energy_wmin", np.float64), ("gco2", np.float64))

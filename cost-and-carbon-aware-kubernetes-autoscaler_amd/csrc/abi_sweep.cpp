@@ -10,7 +10,7 @@ using namespace ccka;
 
 static const ccka_sweep_stat kAllSum = {};  // CCKA_STAT_SUM == 0
 
-static int check_stat(ccka_ctx* c, const ccka_sweep_stat* st) {
+int check_sweep_stat(ccka_ctx* c, const ccka_sweep_stat* st) {
   if (!st) return fail(c, CCKA_EINVAL, "null statistic");
   for (int j = 0; j < 4; ++j) {
     if (st->kind[j] < CCKA_STAT_SUM || st->kind[j] > CCKA_STAT_TAIL)
@@ -50,7 +50,7 @@ static int grid_rows(ccka_ctx* c, const GridSrc& g, const ccka_sweep_stat& st) {
 static int rollout_grids(ccka_ctx* c, int64_t grid_size, const ccka_sweep_stat* st, GridSrc* out) {
   if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
   int rc;
-  if ((rc = check_stat(c, st)) != CCKA_OK) return rc;
+  if ((rc = check_sweep_stat(c, st)) != CCKA_OK) return rc;
   if (grid_size < 1 || c->N % grid_size || c->first_id % grid_size)
     return fail(c, CCKA_EINVAL, "batch (first_id %lld, n %lld) does not hold whole grids of %lld",
                 (long long)c->first_id, (long long)c->N, (long long)grid_size);
@@ -189,7 +189,7 @@ int ccka_debug_grid_stat(ccka_ctx* c, const int64_t* cost, const int32_t* slo, c
                          ccka_grid_stats* out) {
   if (!c || !cost || !slo || !gco2 || !energy || !out) return CCKA_EINVAL;
   int rc;
-  if ((rc = check_stat(c, stat)) != CCKA_OK) return rc;
+  if ((rc = check_sweep_stat(c, stat)) != CCKA_OK) return rc;
   if (n < 1 || grid_size < 1 || n % grid_size)
     return fail(c, CCKA_EINVAL, "%lld scenarios do not hold whole grids of %lld", (long long)n, (long long)grid_size);
   (void)hipSetDevice(c->device);

@@ -123,6 +123,13 @@ struct ccka_ctx {
   Buf<ccka_grid_stats> d_gfront;   // the frontier (local or global)
   // fleet timeline (SEMANTICS 7): the rows of the last ccka_get_timeline
   Buf<ccka_timeline_row> d_tlrows;
+  // paired comparison (SEMANTICS 8): the snapshot [4][snap_n] of a batch's
+  // integer vectors, kept across worlds, scenarios and rollouts (abi_paired.cpp)
+  Buf<int64_t> d_snap;
+  bool have_snap = false;
+  int64_t snap_first = 0, snap_n = 0, snap_grid_size = 0, snap_traces = 0;
+  Buf<ccka_paired_row> d_prows;  // the rows of the last ccka_get_paired
+  Buf<uint32_t> d_pflag;         // its overflow word (and a capture's)
   // learned MLP policy (config 5)
   bool mlp_have_w = false;
   Buf<ccka::mlp_bf16x8> d_w1f;
@@ -213,6 +220,8 @@ ccka::TableParams table_params(const ccka_ctx* c, const double* wc1000, int NW, 
 // abi_rollout.cpp
 int setup_general(ccka_ctx* c, int32_t trajectory, ccka::KParams& k, int* block_out, size_t* lds_out);
 int totals_of(ccka_ctx* c, const ccka::ResultPtrs& res, int64_t N, ccka_totals* out);
+// abi_sweep.cpp: the kinds and q_ppm of a statistic (CCKA_EINVAL, or for a null one)
+int check_sweep_stat(ccka_ctx* c, const ccka_sweep_stat* st);
 // abi_mlp.cpp
 int mlp_alloc(ccka_ctx* c, int64_t n);
 ccka::MlpParams mlp_params(const ccka_ctx* c, int64_t n, int tile);

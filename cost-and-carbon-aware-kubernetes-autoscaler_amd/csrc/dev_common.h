@@ -52,6 +52,18 @@ __device__ __forceinline__ int window_mask(int window_s) {
   return m;
 }
 
+// llrint(x * scale), flagged when it is not representable (NaN or
+// |x * scale| >= 2^63): the fixed-point rule of the totals (util.hip) and of
+// the paired comparison (paired.hip)
+__device__ __forceinline__ long long fix_chk(double x, double scale, long long& ovf) {
+  const double y = x * scale;
+  if (!(y > -9.2233720368547758e18 && y < 9.2233720368547758e18)) {
+    ovf = 1;
+    return 0;
+  }
+  return __double2ll_rn(y);
+}
+
 // Philox-4x32-10 (SEMANTICS.md §4): the load generator, the synthetic MLP
 // states and the sampled policy action all draw from this one text
 __device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

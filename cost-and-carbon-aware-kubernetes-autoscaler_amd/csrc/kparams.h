@@ -435,4 +435,26 @@ hipError_t launch_timeline_sum(const TimelineParams& p, int cus, hipStream_t s);
 // q_value of every row (q_field != NONE; NODES reads the extrema the sums left)
 hipError_t launch_timeline_select(const TimelineParams& p, int cus, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// Paired comparison (paired.hip, SEMANTICS 8): per-position deltas of a batch
+// against a snapshot of an earlier one, reduced per current grid
+// ---------------------------------------------------------------------------
+// snap[4][n] = the integer vectors v of n scenarios' result columns (objective
+// order: cost, SLO minutes, gCO2 ug, energy uW.min); *flag != 0 afterwards when
+// a fixed-point value is not representable
+hipError_t launch_paired_capture(const GridSrc& src, int64_t n, int64_t* snap, uint32_t* flag, hipStream_t s);
+struct PairedParams {
+  GridSrc cur;           // the current columns; first_grid = the global id of its grid 0
+  const int64_t* snap;   // [4][snap_n]
+  int64_t snap_n;
+  int64_t base_off;      // snapshot index of position 0 of row 0's baseline grid
+  int64_t base_step;     // added per row: 0 (one baseline grid for all) or grid_size (SAME)
+  int64_t base_grid;     // global id of row 0's baseline grid (+ row when base_step != 0)
+  int64_t rank[4];       // nearest rank per objective (1 .. grid_size)
+  int32_t kind[4];       // CCKA_STAT_*
+  ccka_paired_row* rows; // [cur.n_grids]
+  uint32_t* flag;        // set on an unrepresentable current value or a subtraction that leaves int64
+};
+hipError_t launch_paired(const PairedParams& p, hipStream_t s);
+
 }  // namespace ccka

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "kparams.h"
+#include "select_dev.h"
 
 namespace ccka {
 
@@ -63,14 +64,9 @@ __global__ void __launch_bounds__(256) grid_stats_kernel(GridSrc g, ccka_grid_st
 // and a 64-lane scan picks the digit that holds the rank. Grids of up to
 // kSelLds scenarios keep their keys in LDS (4 x 8 KiB); larger ones re-read
 // the columns (L2-resident at sweep sizes). SUM objectives are left alone:
-// grid_stats_kernel has written them.
+// grid_stats_kernel has written them. The pass loop is select_dev.h's, which
+// paired_kernel (paired.hip) runs over its deltas too.
 // ---------------------------------------------------------------------------
-constexpr int kSelLds = 1024;
-constexpr int kSelPeel = 2;  // shared digits counted by one add each, per 64 keys
-constexpr uint64_t kSignBit = 0x8000000000000000ull;
-
-__device__ __forceinline__ uint64_t key_i64(int64_t v) { return (uint64_t)v ^ kSignBit; }
-__device__ __forceinline__ int64_t unkey_i64(uint64_t k) { return (int64_t)(k ^ kSignBit); }
 // binary64 by value: negatives flip every bit, the rest flip the sign bit
 __device__ __forceinline__ uint64_t key_f64(double v) {
   const uint64_t b = (uint64_t)__double_as_longlong(v);
@@ -89,14 +85,6 @@ __device__ __forceinline__ uint64_t sel_load_key(const GridSrc& g, int obj, int6
   }
 }
 
-// LDS written by some lanes of this wave, read by others: LDS serves one
-// wave's accesses in order, so only the compiler must not move them
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ void __launch_bounds__(256) grid_select_kernel(GridSel q, ccka_grid_stats* out) {
   __shared__ uint64_t s_key[4][kSelLds];
   __shared__ uint32_t s_hist[4][256];
@@ -109,69 +97,12 @@ __global__ void __launch_bounds__(256) grid_select_kernel(GridSel q, ccka_grid_s
   const int64_t lo = (int64_t)blockIdx.x * n;
   const bool staged = n <= kSelLds;
   uint64_t* keys = s_key[obj];
-  uint32_t* hist = s_hist[obj];
   if (staged)
     for (int64_t i = lane; i < n; i += 64) keys[i] = sel_load_key(g, obj, lo + i);
+  const auto key_at = [&](int64_t i) { return staged ? keys[i] : sel_load_key(g, obj, lo + i); };
 
-  // keys matching (prefix, mask) are the candidates; rank is 1-based among them
-  uint64_t prefix = 0, mask = 0;
-  uint64_t rank = (uint64_t)q.rank[obj];
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    // lane l owns counters 4l .. 4l+3: it clears the four it read last pass
-    *(uint4*)&hist[4 * lane] = make_uint4(0, 0, 0, 0);
-    wave_lds_sync();
-    for (int64_t base = 0; base < n; base += 64) {  // wave-uniform trips: ballots inside
-      const int64_t i = base + lane;
-      uint64_t key = 0;
-      if (i < n) key = staged ? keys[i] : sel_load_key(g, obj, lo + i);
-      const uint32_t digit = (uint32_t)(key >> shift) & 255;
-      bool pending = i < n && (key & mask) == prefix;
-      // Real columns share their high digits and tie heavily (SLO minutes are
-      // mostly 0): 64 lanes adding to one counter serialise in the LDS. kSelPeel
-      // times, the lanes that share the first pending lane's digit are counted
-      // by one add of their number (register traffic only); what is left adds
-      // lane by lane.
-#pragma unroll
-      for (int t = 0; t < kSelPeel; ++t) {
-        if (pending) {
-          const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)digit);
-          const bool same = digit == d0;
-          const uint64_t sm = __ballot(same);  // of the pending lanes
-          if (lane == __ffsll((long long)sm) - 1) atomicAdd(&hist[d0], (uint32_t)__popcll(sm));
-          pending = !same;
-        }
-      }
-      if (pending) atomicAdd(&hist[digit], 1u);
-    }
-    wave_lds_sync();
-    const uint4 c = *(const uint4*)&hist[4 * lane];
-    const uint32_t own_sum = c.x + c.y + c.z + c.w;
-    uint32_t incl = own_sum;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t v = __shfl_up(incl, d);
-      if (lane >= d) incl += v;
-    }
-    const uint32_t excl = incl - own_sum;
-    // exactly one lane's counters hold the rank (the candidates number >= rank)
-    const bool own = excl < rank && rank <= incl;
-    uint32_t digit = 0, below = 0;
-    if (own) {
-      const uint32_t r = (uint32_t)rank - excl;  // 1 .. own_sum
-      if (r <= c.x) { digit = 0; below = 0; }
-      else if (r <= c.x + c.y) { digit = 1; below = c.x; }
-      else if (r <= c.x + c.y + c.z) { digit = 2; below = c.x + c.y; }
-      else { digit = 3; below = c.x + c.y + c.z; }
-      digit += 4 * lane;
-      below += excl;
-    }
-    const int owner = (__ffsll((long long)__ballot(own)) - 1) & 63;
-    digit = __shfl(digit, owner);
-    below = __shfl(below, owner);
-    rank -= below;
-    prefix |= (uint64_t)digit << shift;
-    mask |= 0xffull << shift;
-  }
-  // prefix is the key of x(k)
+  // the pass loop (select_dev.h): prefix is the key of x(k)
+  const uint64_t prefix = wave_radix_select(n, (uint64_t)q.rank[obj], s_hist[obj], lane, key_at);
 
   int64_t ri = unkey_i64(prefix);
   double rd = unkey_f64(prefix);
@@ -179,22 +110,13 @@ __global__ void __launch_bounds__(256) grid_select_kernel(GridSel q, ccka_grid_s
     // values above x(k) in lane-strided index order, then a fixed tree; the
     // ties with x(k) enter as one product (SEMANTICS 6)
     const int64_t terms = n - q.rank[obj] + 1;
-    uint32_t gt = 0;
     if (obj < 2) {
-      uint64_t acc = 0;  // wraps like int64
-      for (int64_t i = lane; i < n; i += 64) {
-        const uint64_t key = staged ? keys[i] : sel_load_key(g, obj, lo + i);
-        if (key > prefix) { acc += (uint64_t)unkey_i64(key); ++gt; }
-      }
-      for (int d = 32; d > 0; d >>= 1) {
-        acc += __shfl_down(acc, d);
-        gt += __shfl_down(gt, d);
-      }
-      ri = (int64_t)(acc + (uint64_t)(terms - (int64_t)gt) * (uint64_t)ri);
+      ri = wave_tail_i64(n, terms, prefix, lane, key_at);
     } else {
+      uint32_t gt = 0;
       double acc = 0.0;
       for (int64_t i = lane; i < n; i += 64) {
-        const double v = unkey_f64(staged ? keys[i] : sel_load_key(g, obj, lo + i));
+        const double v = unkey_f64(key_at(i));
         if (v > rd) { acc += v; ++gt; }
       }
       for (int d = 32; d > 0; d >>= 1) {

@@ -63,15 +63,7 @@ __device__ __forceinline__ void add_chk(long long& a, long long b, long long& ov
   if (__builtin_add_overflow(a, b, &r)) ovf = 1;
   a = r;
 }
-// llrint(x * scale), flagged when it is not representable (|x * scale| >= 2^63)
-__device__ __forceinline__ long long fix_chk(double x, double scale, long long& ovf) {
-  const double y = x * scale;
-  if (!(y > -9.2233720368547758e18 && y < 9.2233720368547758e18)) {
-    ovf = 1;
-    return 0;
-  }
-  return __double2ll_rn(y);
-}
+// fix_chk (dev_common.h): llrint(x * scale), flagged when it is not representable
 
 __global__ void __launch_bounds__(256) totals_partial(TotParams q) {
   __shared__ Part sp[256];

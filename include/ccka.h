@@ -55,7 +55,7 @@ enum ccka_status {
   CCKA_EPARITY = -5,  /* self-check mismatch */
   CCKA_ESTATE = -6,   /* call order (e.g. rollout before set_world) */
   CCKA_ENODEV = -7,   /* no usable gfx950 device */
-  CCKA_EOVERFLOW = -8 /* a fixed-point total would leave int64 (ccka_totals) */
+  CCKA_EOVERFLOW = -8 /* a fixed-point value or total would leave int64 (ccka_totals, paired comparison) */
 };
 
 /* capacity-type bits (karpenter.sh/capacity-type); offering index c: 0 spot, 1 on-demand */
@@ -364,6 +364,43 @@ typedef struct ccka_timeline_row {
                      * values ordered as signed int32; 0 for CCKA_TL_NONE */
 } ccka_timeline_row;
 
+/* Paired comparison (docs/SEMANTICS.md §8): a policy sweep runs every grid over
+ * the same shared traces, so position j of every grid sees the same load
+ * (grid_size a multiple of n_traces > 0). Each scenario has the integer vector
+ * v = (cost_uphmin, slo_minutes as int64, llrint(gco2 * 1e6), llrint(energy_wmin
+ * * 1e6)), the fixed-point rule of ccka_totals. A snapshot keeps the vectors of
+ * a whole batch on the device (ccka_paired_capture); ccka_get_paired reduces,
+ * per current grid, the deltas d[j] = v(current grid, j) - v(baseline grid of
+ * the snapshot, j): negative = better than the baseline. Integers only: every
+ * value is exact and independent of the reduction order. */
+#define CCKA_PAIRED_SAME (-1)   /* base_grid: current grid g against the snapshot's grid g */
+/* stat: per objective (ccka_sweep_stat's order) the order statistic of the
+ * deltas each row also carries. 48 bytes. */
+typedef struct ccka_paired_spec {
+  int64_t grid_size;
+  int64_t base_grid;            /* global grid id inside the snapshot, or CCKA_PAIRED_SAME */
+  ccka_sweep_stat stat;
+} ccka_paired_spec;
+/* One objective of a row. With the grid's deltas sorted ascending and k =
+ * ccka_sweep_rank(pairs, q_ppm): q_value is 0 for SUM, x(k) for QUANTILE, and
+ * for TAIL the sum of the deltas above x(k) plus (pairs - k + 1 - their count)
+ * * x(k), i.e. x(k) + ... + x(pairs). sum and a TAIL wrap mod 2^64 (they cannot
+ * on rollout results). 48 bytes. */
+typedef struct ccka_paired_obj {
+  int64_t sum, min, max, q_value;
+  int64_t n_less, n_greater;    /* positions with d < 0, d > 0; ties = pairs minus both */
+} ccka_paired_obj;
+/* One row per current grid. n_dominates: positions where the current grid is
+ * no worse than the baseline on cost, gCO2 and SLO minutes and better on one
+ * (the frontier's three objectives); n_dominated: the mirror. 232 bytes. */
+typedef struct ccka_paired_row {
+  int64_t grid;                 /* global id of the current grid */
+  int64_t base;                 /* global id of the baseline grid */
+  int64_t pairs;                /* grid_size */
+  int64_t n_dominates, n_dominated;
+  ccka_paired_obj obj[4];       /* cost, SLO minutes, gCO2 (ug), energy (uW.min) */
+} ccka_paired_row;
+
 /* Synthetic load-trace generator (docs/SEMANTICS.md §4). ccka_gen_load accepts
  * the parameters with which every intermediate of §4 stays inside the
  * arithmetic that evaluates it, for every scenario, step and draw, and
@@ -500,6 +537,44 @@ int64_t ccka_timeline_rows(int64_t n, int32_t n_steps, const ccka_timeline_spec*
  * [0, 1000000], grid_size * min(step_bucket, n_steps) > 2^31, more than 2^24
  * rows, or another n_rows. */
 int ccka_get_timeline(ccka_ctx* ctx, const ccka_timeline_spec* spec, ccka_timeline_row* out, int64_t n_rows);
+
+/* ---- paired comparison (docs/SEMANTICS.md §8) -------------------------- */
+/* sizes of ccka_paired_spec, ccka_paired_obj, ccka_paired_row into out[0..n);
+ * returns the count written (ccka_struct_sizes keeps its own list). No context. */
+int32_t ccka_paired_sizes(int64_t* out, int32_t n);
+/* Snapshot of the last rollout's batch: the vectors v of its n scenarios with
+ * first_id, n, grid_size and n_traces (32 bytes per scenario on the device). It
+ * survives ccka_set_world, ccka_set_scenarios, new traces and later rollouts of
+ * any kind, and ends at ccka_close or at the next capture or import (one that
+ * fails its argument checks leaves the earlier snapshot in place, one that
+ * fails later leaves none). CCKA_ESTATE before any
+ * rollout; CCKA_EINVAL unless n_traces > 0, grid_size is a multiple of n_traces,
+ * the batch holds whole grids (first_id and n multiples of grid_size), at most
+ * 2^24 of them, and grid_size <= 2^31; CCKA_EOVERFLOW when a gCO2 or energy
+ * value has no fixed-point form (no snapshot is left then). Which parameters
+ * the positions of a grid share besides the trace (e.g. a per-position cap_sel),
+ * and the trace contents under both batches, are the caller's business. */
+int ccka_paired_capture(ccka_ctx* ctx, int64_t grid_size);
+/* The snapshot's global grid `grid` as a block [4][grid_size] of int64 (objective-
+ * major), count = 4 * grid_size: with ccka_paired_import the transport-free
+ * halves of a baseline shared between ranks whose grids are sharded (as
+ * ccka_totals_pack / _finish are for totals). CCKA_ESTATE without a snapshot. */
+int ccka_paired_export(ccka_ctx* ctx, int64_t grid, int64_t* out, int64_t count);
+/* A one-grid snapshot (global grid id `grid`) from such a block; needs no rollout. */
+int ccka_paired_import(ccka_ctx* ctx, int64_t grid_size, int64_t n_traces, int64_t grid, const int64_t* in,
+                       int64_t count);
+/* out[n_rows], n_rows = n / grid_size: one row per grid of the last rollout's
+ * batch against spec->base_grid of the snapshot (or, CCKA_PAIRED_SAME, each
+ * against the snapshot's grid of the same id), reduced on the device; the
+ * results and the snapshot stay untouched. CCKA_ESTATE before any rollout or
+ * without a snapshot. CCKA_EINVAL for a null argument, n_traces == 0 or
+ * grid_size not a multiple of it, a batch without whole grids, a grid_size or
+ * n_traces other than the snapshot's, a base_grid (or with SAME a current grid)
+ * outside the snapshot, a kind outside 0..2, a non-SUM q_ppm outside
+ * [0, 1000000], another n_rows, more than 2^24 grids, grid_size > 2^31.
+ * CCKA_EOVERFLOW when a current value has no fixed-point form or a subtraction
+ * would leave int64 (it cannot on rollout results, which are non-negative). */
+int ccka_get_paired(ccka_ctx* ctx, const ccka_paired_spec* spec, ccka_paired_row* out, int64_t n_rows);
 
 /* ---- learned MLP control policy (BASELINE config 5) ------------------- */
 /* Weights of the state(64) -> 256 -> 256 -> actions(8) ReLU policy: bf16 bit
