@@ -246,6 +246,46 @@ def paired_dtype():
     return dt
 
 
+class BootSpec(C.Structure):
+    """ccka_boot_spec: the paired bootstrap of docs/SEMANTICS.md 9: grid size and
+    baseline as PairedSpec, the Philox seed, the replicate count B and the two
+    quantiles (ppm) of the replicate sums each row carries as lo and hi."""
+    _fields_ = [("grid_size", C.c_int64), ("base_grid", C.c_int64), ("seed", C.c_uint64),
+                ("replicates", C.c_int32), ("lo_ppm", C.c_int32), ("hi_ppm", C.c_int32), ("_pad", C.c_int32)]
+
+
+class BootObj(C.Structure):
+    """ccka_boot_obj: one objective's observed sum and its replicate sums' interval and sign counts."""
+    _fields_ = [("sum", C.c_int64), ("lo", C.c_int64), ("hi", C.c_int64), ("n_less", C.c_int64),
+                ("n_greater", C.c_int64)]
+
+
+class BootRow(C.Structure):
+    """ccka_boot_row: one current grid of the paired bootstrap."""
+    _fields_ = [("grid", C.c_int64), ("base", C.c_int64), ("pairs", C.c_int64), ("replicates", C.c_int64),
+                ("n_dominates", C.c_int64), ("n_dominated", C.c_int64), ("obj", BootObj * 4)]
+
+
+BOOT_STRUCTS = [BootSpec, BootObj, BootRow]  # the order of ccka_boot_sizes
+BOOT_MAX_REPLICATES = 65536
+
+
+def boot_spec(grid_size, base_grid=PAIRED_SAME, replicates=1000, seed=0, lo_ppm=25000, hi_ppm=975000) -> BootSpec:
+    """BootSpec (the defaults: 1000 replicates, the 2.5 % and 97.5 % points)."""
+    return BootSpec(int(grid_size), int(base_grid), int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicates), int(lo_ppm),
+                    int(hi_ppm), 0)
+
+
+def boot_dtype():
+    """numpy structured dtype laid out exactly as ccka_boot_row: obj is a
+    sub-array of four records in STAT_OBJECTIVES order."""
+    import numpy as np
+    obj = np.dtype([(name, "<i8") for name, _ in BootObj._fields_])
+    dt = np.dtype([(name, "<i8") for name, _ in BootRow._fields_[:-1]] + [("obj", obj, (4,))])
+    assert dt.itemsize == C.sizeof(BootRow)
+    return dt
+
+
 class Detail(C.Structure):
     """ccka_detail: per-pool / base-group / per-deployment breakdown (ccka_set_detail)."""
     _fields_ = [("pool_cost_uphmin", C.c_int64 * MAX_POOLS), ("pool_energy_nwmin", C.c_int64 * MAX_POOLS),
@@ -362,6 +402,8 @@ def load_engine(path: str | None = None):
         "ccka_paired_export": (C.c_int, [vp, C.c_int64, C.c_void_p, C.c_int64]),
         "ccka_paired_import": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
         "ccka_get_paired": (C.c_int, [vp, C.POINTER(PairedSpec), C.c_void_p, C.c_int64]),
+        "ccka_boot_sizes": (C.c_int32, [C.POINTER(C.c_int64), C.c_int32]),
+        "ccka_get_paired_bootstrap": (C.c_int, [vp, C.POINTER(BootSpec), C.c_void_p, C.c_int64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -385,6 +427,7 @@ EXPORTED = [
     "ccka_sweep_rank", "ccka_get_grid_stat", "ccka_pareto_frontier_stat",
     "ccka_timeline_rows", "ccka_get_timeline",
     "ccka_paired_sizes", "ccka_paired_capture", "ccka_paired_export", "ccka_paired_import", "ccka_get_paired",
+    "ccka_boot_sizes", "ccka_get_paired_bootstrap",
 ]
 TOTALS_INT64, TOTALS_BLOCK = 10, 11  # CCKA_TOTALS_INT64, CCKA_TOTALS_BLOCK
 EOVERFLOW = -8
@@ -403,3 +446,8 @@ def check_sizes(lib) -> None:
     got = list(buf[:n])
     if got != want:
         raise CckaError(f"paired struct size mismatch: lib {got} vs python {want}")
+    n = lib.ccka_boot_sizes(buf, 16)
+    want = [C.sizeof(s) for s in BOOT_STRUCTS]
+    got = list(buf[:n])
+    if got != want:
+        raise CckaError(f"bootstrap struct size mismatch: lib {got} vs python {want}")

@@ -321,6 +321,65 @@ class Engine:
                      out.ctypes.data), "ccka_debug_paired")
         return out[:ng]
 
+    # ---- paired bootstrap (docs/SEMANTICS.md 9) ----
+    def paired_bootstrap(self, grid_size: int, base_grid: int = abi.PAIRED_SAME, replicates: int = 1000,
+                         seed: int = 0, lo_ppm: int = 25000, hi_ppm: int = 975000) -> np.ndarray:
+        """One row (abi.boot_dtype()) per grid of the last rollout: the paired
+        bootstrap of its per-position deltas against the snapshot (baseline as
+        paired()): the observed sums and, of `replicates` resampled sums per
+        objective, the lo_ppm and hi_ppm quantiles and the sign and dominance
+        counts (ccka_get_paired_bootstrap)."""
+        spec = abi.boot_spec(grid_size, base_grid, replicates, seed, lo_ppm, hi_ppm)
+        ng = self.n // grid_size if grid_size > 0 else 0
+        out = np.zeros(max(ng, 1), abi.boot_dtype())
+        self._chk(self.lib.ccka_get_paired_bootstrap(self.ctx, C.byref(spec), out.ctypes.data, C.c_int64(ng)),
+                  "ccka_get_paired_bootstrap")
+        return out[:ng]
+
+    def debug_boot(self, cur, base, grid_size: int, base_grid: int = abi.PAIRED_SAME, replicates: int = 1000,
+                   seed: int = 0, lo_ppm: int = 25000, hi_ppm: int = 975000) -> np.ndarray:
+        """Internal: paired_bootstrap()'s kernels on given result columns, as
+        debug_paired(); the context's snapshot stays."""
+        a = [np.ascontiguousarray(cur[k], dt) for k, dt in self.PAIRED_COLUMNS]
+        b = [np.ascontiguousarray(base[k], dt) for k, dt in self.PAIRED_COLUMNS]
+        n, nb = len(a[0]), len(b[0])
+        assert all(x.shape == (n,) for x in a) and all(x.shape == (nb,) for x in b)
+        spec = abi.boot_spec(grid_size, base_grid, replicates, seed, lo_ppm, hi_ppm)
+        ng = n // max(1, grid_size)
+        out = np.zeros(max(ng, 1), abi.boot_dtype())
+        fn = self.lib.ccka_debug_boot
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_int64,
+                       C.POINTER(abi.BootSpec), C.c_void_p]
+        self._chk(fn(self.ctx, *[x.ctypes.data for x in a], n, *[x.ctypes.data for x in b], nb, C.byref(spec),
+                     out.ctypes.data), "ccka_debug_boot")
+        return out[:ng]
+
+    def debug_boot_workspace(self, max_sums: int):
+        """Internal: bound the replicate sums a bootstrap pass holds (0: the
+        default); the rows do not depend on it."""
+        fn = self.lib.ccka_debug_boot_workspace
+        fn.argtypes = [C.c_void_p, C.c_int64]
+        self._chk(fn(self.ctx, max_sums), "ccka_debug_boot_workspace")
+
+    def debug_boot_limits(self):
+        """Internal: (delta staging limit in positions per grid, grid-tile width) of the build."""
+        fn = self.lib.ccka_debug_boot_limits
+        fn.argtypes = [C.POINTER(C.c_int64)]
+        out = (C.c_int64 * 2)()
+        self._chk(fn(out), "ccka_debug_boot_limits")
+        return int(out[0]), int(out[1])
+
+    def debug_boot_ms(self, spec: abi.BootSpec, reps: int = 5, tile: int = 0, stage: int = -1):
+        """Internal: device ms of (boot_delta_kernel, boot_sums_kernel,
+        boot_select_kernel), each alone, for the last rollout against the
+        snapshot; tile / stage select another grid-tile width / staging limit
+        (0 / -1: the build's; stage 0: no LDS staging)."""
+        fn = self.lib.ccka_debug_boot_ms
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BootSpec), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+        ms = (C.c_double * 3)()
+        self._chk(fn(self.ctx, C.byref(spec), reps, tile, stage, ms), "ccka_debug_boot_ms")
+        return tuple(ms)
+
     TOTALS_COLUMNS = (("cost_uphmin", np.int64), ("slo_minutes", np.int32), ("pending_pod_minutes", np.int64),
                       ("node_min_spot", np.int32), ("node_min_od", np.int32), ("launches", np.int32),
                       ("deletions", np.int32), ("energy_wmin", np.float64), ("gco2", np.float64))

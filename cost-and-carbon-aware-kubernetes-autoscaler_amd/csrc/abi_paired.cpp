@@ -12,7 +12,7 @@ constexpr int64_t kPairedMaxGrids = 1 << 24;
 constexpr int64_t kPairedMaxGridSize = (int64_t)1 << 31;  // counts fit 32 bits
 
 // a batch (first_id, n) as whole grids of grid_size whose positions share traces
-static int paired_shape(ccka_ctx* c, int64_t grid_size, int64_t n_traces, int64_t first_id, int64_t n) {
+int paired_shape(ccka_ctx* c, int64_t grid_size, int64_t n_traces, int64_t first_id, int64_t n) {
   if (grid_size < 1 || grid_size > kPairedMaxGridSize)
     return fail(c, CCKA_EINVAL, "grid_size %lld not in [1, 2^31]", (long long)grid_size);
   if (n_traces < 1 || grid_size % n_traces)
@@ -25,7 +25,7 @@ static int paired_shape(ccka_ctx* c, int64_t grid_size, int64_t n_traces, int64_
   return CCKA_OK;
 }
 
-static GridSrc result_columns(const ResultPtrs& r, int64_t grid_size, int64_t first_id, int64_t n) {
+GridSrc result_columns(const ResultPtrs& r, int64_t grid_size, int64_t first_id, int64_t n) {
   GridSrc g{};
   g.cost = r.cost; g.gco2 = r.gco2; g.slo = r.slo; g.energy = r.energy;
   g.grid_size = grid_size;
@@ -35,14 +35,14 @@ static GridSrc result_columns(const ResultPtrs& r, int64_t grid_size, int64_t fi
 }
 
 // *flag (one device word) read back after everything queued on the stream
-static int read_flag(ccka_ctx* c, const uint32_t* flag, uint32_t* out) {
+int read_flag(ccka_ctx* c, const uint32_t* flag, uint32_t* out) {
   HIPCHK(c, hipMemcpyAsync(out, flag, sizeof *out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return CCKA_OK;
 }
 
 // snap[4][g.n_grids * g.grid_size] = the vectors of g's columns; CCKA_EOVERFLOW when one has no fixed-point form
-static int capture_into(ccka_ctx* c, const GridSrc& g, int64_t* snap) {
+int capture_into(ccka_ctx* c, const GridSrc& g, int64_t* snap) {
   if (!c->d_pflag.reserve(1)) return fail(c, CCKA_ENOMEM, "paired overflow word");
   HIPCHK(c, hipMemsetAsync(c->d_pflag, 0, sizeof(uint32_t), c->stream));
   HIPCHK(c, launch_paired_capture(g, g.n_grids * g.grid_size, snap, c->d_pflag, c->stream));
@@ -53,33 +53,48 @@ static int capture_into(ccka_ctx* c, const GridSrc& g, int64_t* snap) {
   return CCKA_OK;
 }
 
-// the kernel's arguments for current columns `cur` against a snapshot of
-// snap_n scenarios from global grid snap_first_grid, under the validated *sp
-static int paired_params(ccka_ctx* c, const GridSrc& cur, const int64_t* snap, int64_t snap_n,
-                         int64_t snap_first_grid, const ccka_paired_spec* sp, PairedParams* out) {
+// the baseline of current columns `cur` in a snapshot of snap_n scenarios from
+// global grid snap_first_grid: one grid of it, or (CCKA_PAIRED_SAME) the grid of the same id
+int paired_baseline(ccka_ctx* c, const GridSrc& cur, int64_t snap_n, int64_t snap_first_grid, int64_t base_grid,
+                    PairedBase* out) {
   const int64_t gs = cur.grid_size, sng = snap_n / gs;
-  PairedParams p{};
-  p.cur = cur;
-  p.snap = snap;
-  p.snap_n = snap_n;
-  if (sp->base_grid == CCKA_PAIRED_SAME) {
+  PairedBase b{};
+  if (base_grid == CCKA_PAIRED_SAME) {
     if (cur.first_grid < snap_first_grid || cur.first_grid + cur.n_grids > snap_first_grid + sng)
       return fail(c, CCKA_EINVAL, "grids [%lld, %lld) are not all inside the snapshot's [%lld, %lld)",
                   (long long)cur.first_grid, (long long)(cur.first_grid + cur.n_grids), (long long)snap_first_grid,
                   (long long)(snap_first_grid + sng));
-    p.base_grid = cur.first_grid;
-    p.base_step = gs;
+    b.grid = cur.first_grid;
+    b.step = gs;
   } else {
-    if (sp->base_grid < snap_first_grid || sp->base_grid >= snap_first_grid + sng)
-      return fail(c, CCKA_EINVAL, "base_grid %lld outside the snapshot's [%lld, %lld)", (long long)sp->base_grid,
+    if (base_grid < snap_first_grid || base_grid >= snap_first_grid + sng)
+      return fail(c, CCKA_EINVAL, "base_grid %lld outside the snapshot's [%lld, %lld)", (long long)base_grid,
                   (long long)snap_first_grid, (long long)(snap_first_grid + sng));
-    p.base_grid = sp->base_grid;
-    p.base_step = 0;
+    b.grid = base_grid;
+    b.step = 0;
   }
-  p.base_off = (p.base_grid - snap_first_grid) * gs;
+  b.off = (b.grid - snap_first_grid) * gs;
+  *out = b;
+  return CCKA_OK;
+}
+
+// the kernel's arguments for current columns `cur` against a snapshot of
+// snap_n scenarios from global grid snap_first_grid, under the validated *sp
+static int paired_params(ccka_ctx* c, const GridSrc& cur, const int64_t* snap, int64_t snap_n,
+                         int64_t snap_first_grid, const ccka_paired_spec* sp, PairedParams* out) {
+  PairedBase b{};
+  int rc;
+  if ((rc = paired_baseline(c, cur, snap_n, snap_first_grid, sp->base_grid, &b)) != CCKA_OK) return rc;
+  PairedParams p{};
+  p.cur = cur;
+  p.snap = snap;
+  p.snap_n = snap_n;
+  p.base_grid = b.grid;
+  p.base_step = b.step;
+  p.base_off = b.off;
   for (int j = 0; j < 4; ++j) {
     p.kind[j] = sp->stat.kind[j];
-    p.rank[j] = p.kind[j] == CCKA_STAT_SUM ? 1 : ccka_sweep_rank(gs, sp->stat.q_ppm[j]);
+    p.rank[j] = p.kind[j] == CCKA_STAT_SUM ? 1 : ccka_sweep_rank(cur.grid_size, sp->stat.q_ppm[j]);
   }
   *out = p;
   return CCKA_OK;
@@ -108,20 +123,56 @@ static int paired_out(ccka_ctx* c, const PairedParams& p, ccka_paired_row* out) 
   return CCKA_OK;
 }
 
+int paired_state(ccka_ctx* c) {
+  if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
+  if (!c->have_snap) return fail(c, CCKA_ESTATE, "no snapshot (ccka_paired_capture / ccka_paired_import)");
+  return CCKA_OK;
+}
+
+int paired_rollout_shape(ccka_ctx* c, int64_t grid_size) {
+  int rc;
+  if ((rc = paired_shape(c, grid_size, c->n_traces, c->first_id, c->N)) != CCKA_OK) return rc;
+  if (grid_size != c->snap_grid_size || c->n_traces != c->snap_traces)
+    return fail(c, CCKA_EINVAL, "grid_size %lld / n_traces %lld differ from the snapshot's %lld / %lld",
+                (long long)grid_size, (long long)c->n_traces, (long long)c->snap_grid_size,
+                (long long)c->snap_traces);
+  return CCKA_OK;
+}
+
 // the last rollout's batch against the context's snapshot: state, then every
 // rule of the spec, all before anything is launched
 static int paired_of_rollout(ccka_ctx* c, const ccka_paired_spec* sp, PairedParams* p) {
-  if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
-  if (!c->have_snap) return fail(c, CCKA_ESTATE, "no snapshot (ccka_paired_capture / ccka_paired_import)");
   int rc;
+  if ((rc = paired_state(c)) != CCKA_OK) return rc;
   if ((rc = check_sweep_stat(c, &sp->stat)) != CCKA_OK) return rc;
-  if ((rc = paired_shape(c, sp->grid_size, c->n_traces, c->first_id, c->N)) != CCKA_OK) return rc;
-  if (sp->grid_size != c->snap_grid_size || c->n_traces != c->snap_traces)
-    return fail(c, CCKA_EINVAL, "grid_size %lld / n_traces %lld differ from the snapshot's %lld / %lld",
-                (long long)sp->grid_size, (long long)c->n_traces, (long long)c->snap_grid_size,
-                (long long)c->snap_traces);
+  if ((rc = paired_rollout_shape(c, sp->grid_size)) != CCKA_OK) return rc;
   return paired_params(c, result_columns(c->res, sp->grid_size, c->first_id, c->N), c->d_snap, c->snap_n,
                        c->snap_first / c->snap_grid_size, sp, p);
+}
+
+int PairedDebugCols::upload(ccka_ctx* c, const int64_t* cost, const int32_t* slo, const double* gco2,
+                            const double* energy, int64_t n, const int64_t* bcost, const int32_t* bslo,
+                            const double* bgco2, const double* benergy, int64_t nb, int64_t gs) {
+  if (gs < 1 || gs > kPairedMaxGridSize || n < 1 || nb < 1 || n % gs || nb % gs || n / gs > kPairedMaxGrids ||
+      nb / gs > kPairedMaxGrids)
+    return fail(c, CCKA_EINVAL, "%lld / %lld scenarios do not hold whole grids of %lld", (long long)n, (long long)nb,
+                (long long)gs);
+  (void)hipSetDevice(c->device);
+  int rc;
+  if ((rc = dupload(c, d_cost, cost, (size_t)n)) != CCKA_OK || (rc = dupload(c, d_slo, slo, (size_t)n)) != CCKA_OK ||
+      (rc = dupload(c, d_gco2, gco2, (size_t)n)) != CCKA_OK || (rc = dupload(c, d_energy, energy, (size_t)n)) != CCKA_OK ||
+      (rc = dupload(c, d_bcost, bcost, (size_t)nb)) != CCKA_OK || (rc = dupload(c, d_bslo, bslo, (size_t)nb)) != CCKA_OK ||
+      (rc = dupload(c, d_bgco2, bgco2, (size_t)nb)) != CCKA_OK ||
+      (rc = dupload(c, d_benergy, benergy, (size_t)nb)) != CCKA_OK)
+    return rc;
+  if (!d_snap.resize(4 * nb)) return fail(c, CCKA_ENOMEM, "snapshot of %lld scenarios", (long long)nb);
+  GridSrc base{};
+  cur = GridSrc{};
+  cur.cost = d_cost; cur.slo = d_slo; cur.gco2 = d_gco2; cur.energy = d_energy;
+  cur.grid_size = gs; cur.n_grids = n / gs;
+  base.cost = d_bcost; base.slo = d_bslo; base.gco2 = d_bgco2; base.energy = d_benergy;
+  base.grid_size = gs; base.n_grids = nb / gs;
+  return capture_into(c, base, d_snap);  // synchronises: the uploads are done whatever it returns
 }
 
 extern "C" {
@@ -216,30 +267,10 @@ int ccka_debug_paired(ccka_ctx* c, const int64_t* cost, const int32_t* slo, cons
     return fail(c, CCKA_EINVAL, "null columns, spec or output");
   int rc;
   if ((rc = check_sweep_stat(c, &spec->stat)) != CCKA_OK) return rc;
-  const int64_t gs = spec->grid_size;
-  if (gs < 1 || gs > kPairedMaxGridSize || n < 1 || nb < 1 || n % gs || nb % gs || n / gs > kPairedMaxGrids ||
-      nb / gs > kPairedMaxGrids)
-    return fail(c, CCKA_EINVAL, "%lld / %lld scenarios do not hold whole grids of %lld", (long long)n, (long long)nb,
-                (long long)gs);
-  (void)hipSetDevice(c->device);
-  DevBuf<int64_t> d_cost, d_bcost, d_snap;
-  DevBuf<int32_t> d_slo, d_bslo;
-  DevBuf<double> d_gco2, d_energy, d_bgco2, d_benergy;
-  if ((rc = dupload(c, d_cost, cost, (size_t)n)) != CCKA_OK || (rc = dupload(c, d_slo, slo, (size_t)n)) != CCKA_OK ||
-      (rc = dupload(c, d_gco2, gco2, (size_t)n)) != CCKA_OK || (rc = dupload(c, d_energy, energy, (size_t)n)) != CCKA_OK ||
-      (rc = dupload(c, d_bcost, bcost, (size_t)nb)) != CCKA_OK || (rc = dupload(c, d_bslo, bslo, (size_t)nb)) != CCKA_OK ||
-      (rc = dupload(c, d_bgco2, bgco2, (size_t)nb)) != CCKA_OK ||
-      (rc = dupload(c, d_benergy, benergy, (size_t)nb)) != CCKA_OK)
-    return rc;
-  if (!d_snap.resize(4 * nb)) return fail(c, CCKA_ENOMEM, "snapshot of %lld scenarios", (long long)nb);
-  GridSrc cur{}, base{};
-  cur.cost = d_cost; cur.slo = d_slo; cur.gco2 = d_gco2; cur.energy = d_energy;
-  cur.grid_size = gs; cur.n_grids = n / gs;
-  base.cost = d_bcost; base.slo = d_bslo; base.gco2 = d_bgco2; base.energy = d_benergy;
-  base.grid_size = gs; base.n_grids = nb / gs;
-  rc = capture_into(c, base, d_snap);  // synchronises: the uploads are done whatever it returns
+  PairedDebugCols cols;
+  rc = cols.upload(c, cost, slo, gco2, energy, n, bcost, bslo, bgco2, benergy, nb, spec->grid_size);
   PairedParams p{};
-  if (rc == CCKA_OK) rc = paired_params(c, cur, d_snap, nb, 0, spec, &p);
+  if (rc == CCKA_OK) rc = paired_params(c, cols.cur, cols.d_snap, nb, 0, spec, &p);
   if (rc == CCKA_OK) rc = paired_launch(c, p);
   if (rc == CCKA_OK) rc = paired_out(c, p, out);
   (void)hipStreamSynchronize(c->stream);  // before the columns are freed

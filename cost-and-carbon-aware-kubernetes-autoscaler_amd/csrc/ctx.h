@@ -130,6 +130,13 @@ struct ccka_ctx {
   int64_t snap_first = 0, snap_n = 0, snap_grid_size = 0, snap_traces = 0;
   Buf<ccka_paired_row> d_prows;  // the rows of the last ccka_get_paired
   Buf<uint32_t> d_pflag;         // its overflow word (and a capture's)
+  // paired bootstrap (SEMANTICS 9, abi_boot.cpp): per pass of grids the deltas
+  // [tiles][grid_size][K][4] and the replicate sums [grids][4][B]; the rows of
+  // the last ccka_get_paired_bootstrap. The overflow word is d_pflag.
+  Buf<int64_t> d_bdelta;
+  Buf<int64_t> d_bsums;
+  Buf<ccka_boot_row> d_brows;
+  int64_t boot_max_sums = 0;  // ccka_debug_boot_workspace: sums per pass (0: kBootMaxSums)
   // learned MLP policy (config 5)
   bool mlp_have_w = false;
   Buf<ccka::mlp_bf16x8> d_w1f;
@@ -222,6 +229,37 @@ int setup_general(ccka_ctx* c, int32_t trajectory, ccka::KParams& k, int* block_
 int totals_of(ccka_ctx* c, const ccka::ResultPtrs& res, int64_t N, ccka_totals* out);
 // abi_sweep.cpp: the kinds and q_ppm of a statistic (CCKA_EINVAL, or for a null one)
 int check_sweep_stat(ccka_ctx* c, const ccka_sweep_stat* st);
+// abi_paired.cpp: the checks and helpers the paired comparison (SEMANTICS 8)
+// shares with the paired bootstrap (abi_boot.cpp)
+int paired_state(ccka_ctx* c);  // CCKA_ESTATE before a rollout or without a snapshot
+// a batch (first_id, n) as whole grids of grid_size whose positions share traces
+int paired_shape(ccka_ctx* c, int64_t grid_size, int64_t n_traces, int64_t first_id, int64_t n);
+// paired_shape of the last rollout's batch, and grid_size / n_traces equal to the snapshot's
+int paired_rollout_shape(ccka_ctx* c, int64_t grid_size);
+ccka::GridSrc result_columns(const ccka::ResultPtrs& r, int64_t grid_size, int64_t first_id, int64_t n);
+struct PairedBase {
+  int64_t grid;  // global id of row 0's baseline grid
+  int64_t step;  // added per row: 0, or grid_size (CCKA_PAIRED_SAME)
+  int64_t off;   // snapshot index of position 0 of row 0's baseline grid
+};
+int paired_baseline(ccka_ctx* c, const ccka::GridSrc& cur, int64_t snap_n, int64_t snap_first_grid,
+                    int64_t base_grid, PairedBase* out);
+int read_flag(ccka_ctx* c, const uint32_t* flag, uint32_t* out);
+int capture_into(ccka_ctx* c, const ccka::GridSrc& g, int64_t* snap);
+// caller-supplied result columns on the device for the debug entry points: `n`
+// current and `nb` baseline scenarios as whole grids of gs (grid ids from 0 on
+// both sides), the baseline captured into a snapshot of its own. upload()
+// synchronises unless it fails on its arguments; the owner synchronises the
+// stream again before the columns go.
+struct PairedDebugCols {
+  ccka::DevBuf<int64_t> d_cost, d_bcost, d_snap;
+  ccka::DevBuf<int32_t> d_slo, d_bslo;
+  ccka::DevBuf<double> d_gco2, d_energy, d_bgco2, d_benergy;
+  ccka::GridSrc cur{};
+  int upload(ccka_ctx* c, const int64_t* cost, const int32_t* slo, const double* gco2, const double* energy,
+             int64_t n, const int64_t* bcost, const int32_t* bslo, const double* bgco2, const double* benergy,
+             int64_t nb, int64_t gs);
+};
 // abi_mlp.cpp
 int mlp_alloc(ccka_ctx* c, int64_t n);
 ccka::MlpParams mlp_params(const ccka_ctx* c, int64_t n, int tile);

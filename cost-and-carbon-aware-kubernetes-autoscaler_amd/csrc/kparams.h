@@ -457,4 +457,41 @@ struct PairedParams {
 };
 hipError_t launch_paired(const PairedParams& p, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// Paired bootstrap (boot.hip, SEMANTICS 9): replicate sums of resampled deltas
+// per grid, then order statistics and sign counts of the sums. One pass covers
+// grids [g0, g0 + gp) of the current columns in tiles of K grids.
+// ---------------------------------------------------------------------------
+constexpr int kBootTile = 2;         // K: grids that share one replicate's indices (profiles/boot/boot_time.json: the A/B)
+constexpr int kBootStage = 1024;     // L: positions per grid the sums kernel keeps in LDS
+constexpr int64_t kBootMaxSums = (int64_t)1 << 25;  // replicate sums per pass (256 MB)
+constexpr int32_t kBootMaxReplicates = 65536;
+constexpr int kBootStagedThreads = 512;  // a staged sums workgroup (8 waves); 256 where it gathers from `delta`
+struct BootParams {
+  GridSrc cur;           // as PairedParams
+  const int64_t* snap;   // [4][snap_n]
+  int64_t snap_n, base_off, base_step, base_grid;
+  int64_t g0, gp;        // this pass: grids [g0, g0 + gp) of cur
+  int64_t* delta;        // [tiles][grid_size][K][4]: the pass's deltas; slots past gp hold 0
+  int64_t* sums;         // [gp][4][B] replicate sums
+  ccka_boot_row* rows;   // [cur.n_grids]
+  uint32_t* flag;        // as PairedParams
+  int64_t rank_lo, rank_hi;  // nearest ranks among the B sums (1 .. B)
+  uint32_t k0, k1;       // the Philox key: seed's low and high word
+  int32_t B;             // replicates
+  int32_t K;             // grids per tile: 1, 2, 4 or 8
+  int32_t L;             // staging limit of the sums kernel's instantiation (0: gather from `delta`)
+  int32_t chunks;        // replicate chunks per tile (one workgroup each)
+  int32_t per_chunk;     // replicates per chunk
+  int32_t _pad;
+};
+// whether (K, L) names an instantiation of boot_sums_kernel
+bool boot_config_ok(int K, int L);
+// delta[...] of the pass; the flag is set on an unrepresentable value or difference
+hipError_t launch_boot_delta(const BootParams& p, hipStream_t s);
+// sums[...] of the pass from its deltas
+hipError_t launch_boot_sums(const BootParams& p, hipStream_t s);
+// rows[g0 .. g0 + gp) from the pass's sums and deltas
+hipError_t launch_boot_select(const BootParams& p, hipStream_t s);
+
 }  // namespace ccka

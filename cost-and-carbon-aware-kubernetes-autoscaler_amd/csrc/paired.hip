@@ -17,6 +17,7 @@
 
 #include "dev_common.h"
 #include "kparams.h"
+#include "paired_dev.h"
 #include "select_dev.h"
 
 #pragma clang fp contract(off)
@@ -26,16 +27,6 @@ namespace ccka {
 static_assert(sizeof(ccka_paired_spec) == 48 && sizeof(ccka_paired_obj) == 48 && sizeof(ccka_paired_row) == 232,
               "paired comparison ABI layout");
 
-// objective o of scenario idx as its integer (SEMANTICS 8: units)
-__device__ __forceinline__ long long paired_value(const GridSrc& g, int o, int64_t idx, long long& ovf) {
-  switch (o) {
-    case 0: return g.cost[idx];
-    case 1: return (long long)g.slo[idx];
-    case 2: return fix_chk(g.gco2[idx], 1e6, ovf);
-    default: return fix_chk(g.energy[idx], 1e6, ovf);
-  }
-}
-
 __global__ void __launch_bounds__(256) paired_capture_kernel(GridSrc g, int64_t n, int64_t* __restrict__ snap,
                                                              uint32_t* flag) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -44,13 +35,6 @@ __global__ void __launch_bounds__(256) paired_capture_kernel(GridSrc g, int64_t 
 #pragma unroll
   for (int o = 0; o < 4; ++o) snap[o * n + i] = paired_value(g, o, i, ovf);
   if (ovf) atomicOr(flag, 1u);
-}
-
-// a - b, flagged instead of wrapped
-__device__ __forceinline__ long long sub_chk(long long a, long long b, long long& ovf) {
-  long long r;
-  if (__builtin_sub_overflow(a, b, &r)) ovf = 1;
-  return r;
 }
 
 // one lane's running reduction of one objective's deltas

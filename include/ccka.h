@@ -401,6 +401,40 @@ typedef struct ccka_paired_row {
   ccka_paired_obj obj[4];       /* cost, SLO minutes, gCO2 (ug), energy (uW.min) */
 } ccka_paired_row;
 
+/* Paired bootstrap (docs/SEMANTICS.md §9): how far the sum of a grid's deltas
+ * moves under another draw of the positions. Replicate r resamples the
+ * positions with replacement (Philox-4x32-10 under `seed`; the indices depend
+ * on neither the grid nor the objective) and sums the drawn deltas; the row
+ * carries order statistics and sign counts of the `replicates` sums. Integers
+ * only, as §8. 40 bytes. */
+typedef struct ccka_boot_spec {
+  int64_t grid_size;
+  int64_t base_grid;            /* as ccka_paired_spec */
+  uint64_t seed;
+  int32_t replicates;           /* B, 1 .. 65536 */
+  int32_t lo_ppm, hi_ppm;       /* 0 <= lo_ppm <= hi_ppm <= 1000000 */
+  int32_t _pad;                 /* 0 */
+} ccka_boot_spec;
+/* One objective of a row. sum: the observed sum of the deltas (ccka_get_paired's).
+ * With the B replicate sums sorted ascending as signed int64: lo = x(k_lo), hi =
+ * x(k_hi), k = ccka_sweep_rank(B, ppm). n_less / n_greater: replicates whose
+ * sum is < 0 / > 0. Sums wrap mod 2^64 (they cannot on rollout results). 40 bytes. */
+typedef struct ccka_boot_obj {
+  int64_t sum, lo, hi;
+  int64_t n_less, n_greater;
+} ccka_boot_obj;
+/* One row per current grid. n_dominates: replicates whose sums are <= 0 on
+ * cost, gCO2 and SLO minutes and < 0 on at least one; n_dominated: the mirror.
+ * 208 bytes. */
+typedef struct ccka_boot_row {
+  int64_t grid;                 /* global id of the current grid */
+  int64_t base;                 /* global id of the baseline grid */
+  int64_t pairs;                /* grid_size */
+  int64_t replicates;           /* B */
+  int64_t n_dominates, n_dominated;
+  ccka_boot_obj obj[4];         /* cost, SLO minutes, gCO2 (ug), energy (uW.min) */
+} ccka_boot_row;
+
 /* Synthetic load-trace generator (docs/SEMANTICS.md §4). ccka_gen_load accepts
  * the parameters with which every intermediate of §4 stays inside the
  * arithmetic that evaluates it, for every scenario, step and draw, and
@@ -575,6 +609,21 @@ int ccka_paired_import(ccka_ctx* ctx, int64_t grid_size, int64_t n_traces, int64
  * CCKA_EOVERFLOW when a current value has no fixed-point form or a subtraction
  * would leave int64 (it cannot on rollout results, which are non-negative). */
 int ccka_get_paired(ccka_ctx* ctx, const ccka_paired_spec* spec, ccka_paired_row* out, int64_t n_rows);
+
+/* ---- paired bootstrap (docs/SEMANTICS.md §9) ---------------------------- */
+/* sizes of ccka_boot_spec, ccka_boot_obj, ccka_boot_row into out[0..n); returns
+ * the count written. No context. */
+int32_t ccka_boot_sizes(int64_t* out, int32_t n);
+/* out[n_rows], n_rows = n / grid_size: per grid of the last rollout's batch the
+ * paired bootstrap of its deltas against the snapshot (baseline as
+ * ccka_get_paired), resampled, summed and selected on the device. A grid's row
+ * depends only on that grid, its baseline and the spec: it is the same in any
+ * batch or shard that holds the grid. The results, the snapshot and the sweep
+ * statistics stay untouched. State and errors are ccka_get_paired's (without
+ * its statistic); also CCKA_EINVAL for replicates outside [1, 65536], a ppm
+ * outside [0, 1000000], lo_ppm > hi_ppm or _pad != 0. Every check runs before
+ * anything is launched. */
+int ccka_get_paired_bootstrap(ccka_ctx* ctx, const ccka_boot_spec* spec, ccka_boot_row* out, int64_t n_rows);
 
 /* ---- learned MLP control policy (BASELINE config 5) ------------------- */
 /* Weights of the state(64) -> 256 -> 256 -> actions(8) ReLU policy: bf16 bit
