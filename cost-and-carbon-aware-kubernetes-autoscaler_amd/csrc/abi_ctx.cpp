@@ -408,6 +408,18 @@ int ccka_open(ccka_ctx** out, int device_ordinal) {
   return CCKA_OK;
 }
 
+// no result of an earlier run is readable any more: the result columns, the
+// trajectory, the detail, the closed loop's records and samples, the timing
+static void end_results(ccka_ctx* c) {
+  c->ran = false;
+  c->res_valid = false;
+  c->traj_valid = false;
+  c->detail_valid = false;
+  c->pol_rec_valid = false;
+  c->pol_feat_valid = false;
+  c->pg_valid = false;
+}
+
 static void free_results(ccka_ctx* c) {
   c->d_res.release();
   c->res = ResultPtrs{};
@@ -489,6 +501,15 @@ int ccka_set_world(ccka_ctx* c, const ccka_world* w) {
     return fail(c, CCKA_EINVAL, "hpa_sync_s must be 0, 10, 15, 20, 30 or 60");
   for (int q = 0; q < w->n_pools; ++q)
     if (w->pools[q].limit_mem_mi < -1) return fail(c, CCKA_EINVAL, "pool %d limit_mem_mi invalid", q);
+  // the world is accepted. Everything computed for the earlier one ends here,
+  // before hw is replaced (ccka.h, "what ends what"), so that a failure below
+  // (CCKA_ENOMEM, CCKA_EHIP) leaves no world rather than the new hw beside the
+  // earlier set and results. The scenario set ends too: its region ids were
+  // checked against the earlier n_regions, so the next step is ccka_set_scenarios
+  c->have_world = false;
+  c->have_sc = false;
+  c->have_load = false;
+  end_results(c);
   c->hw = *w;
   const int K = w->n_types, Z = w->n_zones, R = w->n_regions;
   int rc;
@@ -510,9 +531,6 @@ int ccka_set_world(ccka_ctx* c, const ccka_world* w) {
   if ((rc = d1_check_world(c)) != CCKA_OK) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->have_world = true;
-  c->have_load = false;
-  c->traj_valid = false;
-  c->ran = false;
   return CCKA_OK;
 }
 
@@ -630,7 +648,7 @@ int ccka_set_scenarios(ccka_ctx* c, const ccka_scenarios* sc) {
   c->n_traces = sc->n_traces;
   if ((rc = alloc_results(c)) != CCKA_OK) return rc;
   c->have_sc = true;
-  c->ran = false;
+  end_results(c);
   return CCKA_OK;
 }
 

@@ -92,7 +92,7 @@ int ccka_debug_last_engine(ccka_ctx* c, int32_t* engine, double* table_ms) {
 int ccka_debug_last_plan(ccka_ctx* c, int32_t out[12]) {
   static_assert(PLAN_FIELDS == 12, "ccka_debug_last_plan's out[12]");
   if (!c || !out) return CCKA_EINVAL;
-  if (!c->ran || c->last_engine == 3 || c->last_engine == 4) return fail(c, CCKA_ESTATE, "no whole-horizon rollout ran last");
+  if (!c->res_valid || c->last_engine == 3 || c->last_engine == 4) return fail(c, CCKA_ESTATE, "no whole-horizon rollout ran last");
   std::copy(c->last_plan, c->last_plan + PLAN_FIELDS, out);
   return CCKA_OK;
 }

@@ -124,7 +124,7 @@ static int paired_out(ccka_ctx* c, const PairedParams& p, ccka_paired_row* out) 
 }
 
 int paired_state(ccka_ctx* c) {
-  if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
+  if (!c->res_valid) return fail(c, CCKA_ESTATE, "no rollout yet");
   if (!c->have_snap) return fail(c, CCKA_ESTATE, "no snapshot (ccka_paired_capture / ccka_paired_import)");
   return CCKA_OK;
 }
@@ -186,7 +186,7 @@ int32_t ccka_paired_sizes(int64_t* out, int32_t n) {
 
 int ccka_paired_capture(ccka_ctx* c, int64_t grid_size) {
   if (!c) return CCKA_EINVAL;
-  if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
+  if (!c->res_valid) return fail(c, CCKA_ESTATE, "no rollout yet");
   int rc;
   if ((rc = paired_shape(c, grid_size, c->n_traces, c->first_id, c->N)) != CCKA_OK) return rc;
   (void)hipSetDevice(c->device);

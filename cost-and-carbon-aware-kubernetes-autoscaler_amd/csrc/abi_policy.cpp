@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "host_rules.h"
 
 using namespace ccka;
 
@@ -49,13 +50,15 @@ static int policy_tables(ccka_ctx* c, KParams& k) {
 }
 
 // a loop's launches are on the stream: what it left valid, then its timing
-static int loop_done(ccka_ctx* c, int engine, int32_t trajectory, int32_t record) {
+static int loop_done(ccka_ctx* c, int engine, int32_t trajectory, int32_t record, bool feat) {
   c->last_engine = engine;
   c->traj_nt = false;
   c->traj_valid = trajectory != 0;
   c->detail_valid = c->detail_on;
   c->pol_rec_valid = record != 0;
+  c->pol_feat_valid = feat;
   c->ran = true;
+  c->res_valid = true;
   return ccka_sync(c);
 }
 
@@ -65,8 +68,10 @@ static int loop_done(ccka_ctx* c, int engine, int32_t trajectory, int32_t record
 // step are kept for the score-function gradient (ccka_policy_grad).
 static int policy_loop(ccka_ctx* c, int32_t trajectory, int32_t record, const ccka_pg_params* pg) {
   if (!c) return CCKA_EINVAL;
-  c->pg_valid = false;  // the recorded features / actions are about to be overwritten
   if (!c->have_world || !c->have_sc) return fail(c, CCKA_ESTATE, "world/scenarios not set");
+  if (!c->have_load) return fail(c, CCKA_ESTATE, "no load traces (ccka_set_load / ccka_gen_load)");
+  if (!c->mlp_have_w) return fail(c, CCKA_ESTATE, "MLP weights not set (ccka_mlp_set_weights)");
+  (void)hipSetDevice(c->device);
   // the single-deployment kernel's tiled trace copy (N*T*4 bytes) and the
   // skewed schedule's scenario-major one are not read here: released for the
   // loop's own arrays, rebuilt by the next rollout
@@ -74,9 +79,6 @@ static int policy_loop(ccka_ctx* c, int32_t trajectory, int32_t record, const cc
   c->load_w_lpw = 0;
   c->d_load_nt.release();
   c->load_nt_dp = 0;
-  if (!c->have_load) return fail(c, CCKA_ESTATE, "no load traces (ccka_set_load / ccka_gen_load)");
-  if (!c->mlp_have_w) return fail(c, CCKA_ESTATE, "MLP weights not set (ccka_mlp_set_weights)");
-  (void)hipSetDevice(c->device);
   const ccka_world& w = c->hw;
   const int64_t N = c->N;
   const int T = w.n_steps;
@@ -92,7 +94,10 @@ static int policy_loop(ccka_ctx* c, int32_t trajectory, int32_t record, const cc
     return fail(c, CCKA_ENOMEM, "policy state alloc (%lld words)", (long long)(words * N));
   if (!all_or_none(c->d_pol_target.reserve(N) && c->d_pol_cw.reserve(N), c->d_pol_target, c->d_pol_cw))
     return fail(c, CCKA_ENOMEM, "policy action alloc");
+  // the recorded actions, features and samples are about to be overwritten
   c->pol_rec_valid = false;
+  c->pol_feat_valid = false;
+  c->pg_valid = false;
   const int64_t TN = (int64_t)T * N;
   if (record && !all_or_none(c->d_rec_target.reserve(TN) && c->d_rec_cw.reserve(TN), c->d_rec_target, c->d_rec_cw))
     return fail(c, CCKA_ENOMEM, "policy action record alloc");
@@ -131,7 +136,7 @@ static int policy_loop(ccka_ctx* c, int32_t trajectory, int32_t record, const cc
       HIPCHK(c, hipEventRecord(c->ev_mid, c->stream));
       HIPCHK(c, launch_rollout_policy(k, off + mlp_lds, pg ? 2 : 1, c->stream));
       HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-      return loop_done(c, 4, trajectory, record);
+      return loop_done(c, 4, trajectory, record, feat_on);
     }
   }
   // ---- the launched loop: the general kernel one step per launch, the
@@ -236,7 +241,7 @@ static int policy_loop(ccka_ctx* c, int32_t trajectory, int32_t record, const cc
     HIPCHK(c, hipGraphLaunch(c->pol_graph, c->stream));
   }
   HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-  return loop_done(c, 3, trajectory, record);
+  return loop_done(c, 3, trajectory, record, feat_on);
 }
 
 extern "C" {
@@ -343,16 +348,19 @@ static int pg_copy_grads(ccka_ctx* c, ccka_mlp_grads* out) {
 int ccka_mlp_backward(ccka_ctx* c, const uint16_t* x, const uint8_t* actions, const float* coef, int64_t m,
                       ccka_mlp_grads* out) {
   if (!c || !x || !actions || !coef || !out || m < 1) return CCKA_EINVAL;
+  // every state and argument check before the first buffer is touched: the
+  // rows go through the samples' buffers, and a failing call changes nothing
+  if (!c->mlp_have_w) return fail(c, CCKA_ESTATE, "MLP weights not set (ccka_mlp_set_weights)");
+  for (int64_t i = 0; i < m; ++i)
+    if (actions[i] >= MLP_OUT) return fail(c, CCKA_EINVAL, "action %d of row %lld out of range", actions[i], (long long)i);
   (void)hipSetDevice(c->device);
+  c->pg_valid = false;  // the recorded samples of ccka_policy_grad are gone
   if (!c->d_pg_x.reserve(m * MLP_IN)) return fail(c, CCKA_ENOMEM, "backward rows alloc");
   if (!c->d_pg_act.reserve(m)) return fail(c, CCKA_ENOMEM, "action alloc");
   if (!c->d_pg_coef.reserve(m)) return fail(c, CCKA_ENOMEM, "coef alloc");
-  for (int64_t i = 0; i < m; ++i)
-    if (actions[i] >= MLP_OUT) return fail(c, CCKA_EINVAL, "action %d of row %lld out of range", actions[i], (long long)i);
   HIPCHK(c, hipMemcpyAsync(c->d_pg_x, x, (size_t)m * MLP_IN * 2, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_pg_act, actions, (size_t)m, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_pg_coef, coef, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
-  c->pg_valid = false;  // the recorded samples of ccka_policy_grad are gone
   int rc;
   if ((rc = pg_backward(c, c->d_pg_x, c->d_pg_act, c->d_pg_coef, m, m)) != CCKA_OK) return rc;
   return pg_copy_grads(c, out);
@@ -415,6 +423,8 @@ int ccka_get_policy_samples(ccka_ctx* c, uint8_t* actions, float* coef, int64_t 
   if (!c || !actions || !coef) return CCKA_EINVAL;
   if (!c->pg_valid) return fail(c, CCKA_ESTATE, "no ccka_policy_grad samples");
   if (count != c->pg_T * c->N) return fail(c, CCKA_EINVAL, "sample count mismatch");
+  if (!copy_fits(count, c->d_pg_act.count()) || !copy_fits(c->N, c->d_pg_coef.count()))
+    return fail(c, CCKA_ESTATE, "sample records smaller than this batch");
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipMemcpyAsync(actions, c->d_pg_act, (size_t)count, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(coef, c->d_pg_coef, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->stream));
@@ -426,6 +436,8 @@ int ccka_get_policy_actions(ccka_ctx* c, int16_t* target, double* cw, int64_t co
   if (!c || !target || !cw) return CCKA_EINVAL;
   if (!c->pol_rec_valid) return fail(c, CCKA_ESTATE, "last run recorded no policy actions");
   if (count != (int64_t)c->hw.n_steps * c->N) return fail(c, CCKA_EINVAL, "action count != T x N");
+  if (!copy_fits(count, c->d_rec_target.count()) || !copy_fits(count, c->d_rec_cw.count()))
+    return fail(c, CCKA_ESTATE, "action records smaller than this batch");
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipMemcpyAsync(target, c->d_rec_target, (size_t)count * 2, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(cw, c->d_rec_cw, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream));
@@ -443,8 +455,9 @@ int ccka_debug_policy_features(ccka_ctx* c, int32_t enable) {
 
 int ccka_debug_get_policy_features(ccka_ctx* c, uint16_t* out, int64_t count) {
   if (!c || !out) return CCKA_EINVAL;
-  if (!(c->pol_feat_on || c->pg_valid) || !c->pol_rec_valid) return fail(c, CCKA_ESTATE, "no recorded features");
+  if (!c->pol_feat_valid || !c->pol_rec_valid) return fail(c, CCKA_ESTATE, "no recorded features");
   if (count != (int64_t)(c->hw.n_steps + 1) * c->N * 64) return fail(c, CCKA_EINVAL, "feature count mismatch");
+  if (!copy_fits(count, c->d_feat_rec.count())) return fail(c, CCKA_ESTATE, "feature records smaller than this batch");
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipMemcpyAsync(out, c->d_feat_rec, (size_t)count * 2, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

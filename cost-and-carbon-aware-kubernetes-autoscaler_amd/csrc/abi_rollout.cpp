@@ -309,6 +309,7 @@ int ccka_rollout_async(ccka_ctx* c, int32_t trajectory) {
   c->traj_valid = trajectory != 0;
   c->detail_valid = c->detail_on;
   c->ran = true;
+  c->res_valid = true;
   return CCKA_OK;
 }
 
@@ -320,7 +321,7 @@ int ccka_set_detail(ccka_ctx* c, int32_t on) {
 
 int ccka_get_detail(ccka_ctx* c, ccka_detail* out, int64_t count) {
   if (!c || !out) return CCKA_EINVAL;
-  if (!c->ran || !c->detail_valid) return fail(c, CCKA_ESTATE, "last rollout recorded no detail (ccka_set_detail)");
+  if (!c->res_valid || !c->detail_valid) return fail(c, CCKA_ESTATE, "last rollout recorded no detail (ccka_set_detail)");
   if (count != c->N) return fail(c, CCKA_EINVAL, "detail count %lld != %lld scenarios", (long long)count, (long long)c->N);
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipMemcpy2DAsync(out, sizeof(ccka_detail), c->d_detail, sizeof(DetailDev), sizeof(ccka_detail), (size_t)count,
@@ -358,7 +359,7 @@ int ccka_last_kernel_ms(ccka_ctx* c, double* ms) {
 
 int ccka_get_results(ccka_ctx* c, ccka_results* o) {
   if (!c || !o) return CCKA_EINVAL;
-  if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
+  if (!c->res_valid) return fail(c, CCKA_ESTATE, "no rollout yet");
   (void)hipSetDevice(c->device);
   const size_t n = (size_t)c->N;
   const ResultPtrs& k = c->res;
@@ -427,7 +428,7 @@ int ccka_get_trajectory_native(ccka_ctx* c, ccka_traj_rec* out, int64_t count, i
 
 int ccka_get_totals(ccka_ctx* c, ccka_totals* out) {
   if (!c || !out) return CCKA_EINVAL;
-  if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
+  if (!c->res_valid) return fail(c, CCKA_ESTATE, "no rollout yet");
   (void)hipSetDevice(c->device);
   return totals_of(c, c->res, c->N, out);
 }

@@ -48,7 +48,7 @@ static int grid_rows(ccka_ctx* c, const GridSrc& g, const ccka_sweep_stat& st) {
 
 // the last rollout's result columns as whole grids of grid_size
 static int rollout_grids(ccka_ctx* c, int64_t grid_size, const ccka_sweep_stat* st, GridSrc* out) {
-  if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
+  if (!c->res_valid) return fail(c, CCKA_ESTATE, "no rollout yet");
   int rc;
   if ((rc = check_sweep_stat(c, st)) != CCKA_OK) return rc;
   if (grid_size < 1 || c->N % grid_size || c->first_id % grid_size)

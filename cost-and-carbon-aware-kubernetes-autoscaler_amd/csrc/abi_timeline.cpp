@@ -58,7 +58,7 @@ static int timeline_run(ccka_ctx* c, const ccka_traj_rec* recs, int64_t n, int32
 // caller's row count (want_rows >= 0), all before anything is launched
 static int timeline_of_rollout(ccka_ctx* c, const ccka_timeline_spec* sp, int64_t want_rows, int64_t* rows,
                                TimelineParams* p) {
-  if (!c->ran) return fail(c, CCKA_ESTATE, "no rollout yet");
+  if (!c->res_valid) return fail(c, CCKA_ESTATE, "no rollout yet");
   if (!c->traj_valid) return fail(c, CCKA_ESTATE, "last rollout had no trajectory");
   const int32_t T = c->hw.n_steps;
   if (c->d_traj.count() != (int64_t)T * c->N) return fail(c, CCKA_ESTATE, "trajectory does not match the batch");

@@ -75,7 +75,8 @@ struct ccka_ctx {
   ncclComm_t comm = nullptr;
   double last_ms = 0.0;        // rollout kernel (HIP events on the engine stream)
   double last_table_ms = 0.0;  // argmin-table kernel of the same rollout
-  bool ran = false;
+  bool ran = false;        // a timed launch exists (ccka_sync / ccka_last_kernel_ms): rollout, loop or MLP forward
+  bool res_valid = false;  // the result columns hold a run of this world and scenario set (every results getter)
   // single-deployment engine (rollout_d1.hip): world digest, argmin tables
   bool d1_world = false;     // the world qualifies (d1_check_world)
   bool d1_ready = false;     // scenario-dependent part prepared
@@ -163,6 +164,7 @@ struct ccka_ctx {
   Buf<int16_t> d_rec_target;
   Buf<double> d_rec_cw;
   bool pol_rec_valid = false;
+  bool pol_feat_valid = false;  // the last loop kept its features (the switch was on, or ccka_policy_grad)
   bool pol_feat_on = false;
   // the closed loop's launch sequence captured as one hipGraph, replayed while
   // its inputs (launch parameters, buffers, sizes) are unchanged

@@ -242,6 +242,12 @@ static void test_host_rules() {
   CHECK(traj_stage_cap(1000, dflt * 10, 0) == dflt && traj_stage_cap(dflt + 7, (dflt + 7) * 4, 0) == dflt + 7);
   CHECK(ccka::trace_tile_count(65, 5, 64) == 5 * 128 && ccka::trace_tile_count(64, 5, 64) == 5 * 64);
   CHECK(ccka::trace_nt_count(65, 5, 4) == 65 * 5 * 4);
+  // a getter's copy against its grow-only buffer: all of it is the last
+  // accepted count, one more the first rejected; nothing from an empty buffer
+  using ccka::copy_fits;
+  CHECK(copy_fits(120 * 64, 120 * 64) && copy_fits(40 * 64, 120 * 64) && copy_fits(0, 0));
+  CHECK(!copy_fits(120 * 64 + 1, 120 * 64) && !copy_fits(1, 0) && !copy_fits(-1, 10));
+  CHECK(copy_fits(INT64_MAX, INT64_MAX) && !copy_fits(INT64_MAX, INT64_MAX - 1));
 }
 
 int main() {

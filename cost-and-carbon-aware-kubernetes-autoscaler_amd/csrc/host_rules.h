@@ -88,6 +88,13 @@ inline int64_t traj_stage_cap(int64_t N, int64_t count, int64_t stage) {
   return cap > N ? cap : N;
 }
 
+// A read-back of `want` elements from a buffer that holds `have`: the last
+// check of every getter whose buffer only grows (the closed loop's records,
+// the samples), after the validity flag and the caller's count. The flags end
+// with the world and the scenario set, so this never fails today; it is what
+// keeps a copy inside its allocation if a flag is ever left standing.
+inline bool copy_fits(int64_t want, int64_t have) { return want >= 0 && want <= have; }
+
 // element counts of the two trace copies (util.hip: trace_tile_kernel, trace_nt_kernel)
 inline int64_t trace_tile_count(int64_t N, int64_t T, int64_t lpw) { return T * ((N + lpw - 1) / lpw * lpw); }
 inline int64_t trace_nt_count(int64_t NL, int64_t T, int64_t DP) { return NL * T * DP; }

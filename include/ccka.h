@@ -474,8 +474,57 @@ int ccka_open(ccka_ctx** out, int device_ordinal);
 void ccka_close(ccka_ctx* ctx);
 const char* ccka_last_error(const ccka_ctx* ctx);
 
+/* ---- what ends what -----------------------------------------------------
+ * A context holds readable things: the scenario set, the load, the results
+ * (ccka_get_results, ccka_get_totals, the grid statistics, the Pareto calls,
+ * ccka_paired_capture, ccka_get_paired, ccka_get_paired_bootstrap), the
+ * trajectory (ccka_get_trajectory[_native], ccka_trajectory_layout,
+ * ccka_get_timeline), the detail, the closed loop's recorded actions
+ * (ccka_get_policy_actions) and recorded features, the policy-gradient samples
+ * (ccka_get_policy_samples), the paired snapshot, the MLP weights and states,
+ * and the time of the last launch (ccka_last_kernel_ms). A call that returns
+ * CCKA_OK ends some of them and keeps the rest:
+ *
+ *   ccka_set_world        ends the scenario set (the next step is
+ *                         ccka_set_scenarios: its region ids are checked
+ *                         against this world), the load, the results, the
+ *                         trajectory, the detail, the recorded actions and
+ *                         features, the samples, the launch time.
+ *                         Keeps the snapshot (SEMANTICS §8), the MLP weights
+ *                         and states, the switches (ccka_set_detail, debug).
+ *   ccka_set_scenarios    ends the load, the results, the trajectory, the
+ *                         detail, the recorded actions and features, the
+ *                         samples, the launch time. Keeps the world, the
+ *                         snapshot, the MLP weights and states.
+ *   ccka_set_load,        end nothing readable (both derived trace copies are
+ *   ccka_gen_load         rebuilt): the results stay the last run's.
+ *   ccka_rollout[_async]  ends the trajectory unless asked for, and the detail
+ *                         unless it is on. Keeps the recorded actions and
+ *                         features and the samples: they are the last loop's,
+ *                         and no rollout touches their buffers.
+ *   ccka_policy_rollout   ends the samples; the recorded actions unless
+ *                         `record`; the recorded features unless the feature
+ *                         switch is on; the trajectory unless `trajectory`;
+ *                         the detail unless it is on. Its last step's
+ *                         features replace the MLP states.
+ *   ccka_policy_grad      ends the trajectory (and the detail unless it is
+ *                         on); the actions, features and samples are now this
+ *                         loop's. The MLP states as above.
+ *   ccka_mlp_backward     ends the samples (its rows go through their buffers).
+ *   ccka_mlp_forward[_async], ccka_debug_mlp_batch
+ *                         end nothing: they are timed launches only
+ *                         (ccka_sync, ccka_last_kernel_ms), never results.
+ *
+ * A call that fails its argument or state checks (CCKA_EINVAL, CCKA_ESTATE)
+ * changes nothing, with one exception: a failing ccka_set_scenarios ends the
+ * earlier set and its load (the results of the last run stay readable).
+ * A getter whose object has ended returns CCKA_ESTATE before it looks at a
+ * count: never CCKA_EINVAL on a count formed from the new shape. The recorded
+ * features are read together with the recorded actions. */
+
 /* ---- inputs ---------------------------------------------------------- */
-/* Validate and upload the world (catalog, tiles, pools, deployments). */
+/* Validate and upload the world (catalog, tiles, pools, deployments). Ends
+ * the scenario set: ccka_set_scenarios comes next (above). */
 int ccka_set_world(ccka_ctx* ctx, const ccka_world* world);
 /* Upload per-scenario parameters (resets any previous batch). */
 int ccka_set_scenarios(ccka_ctx* ctx, const ccka_scenarios* sc);
